@@ -26,9 +26,12 @@ streams (independent files shard per GPU, no collective on the data path:
 
 Output: ONE JSON line on rank 0 (the driver's contract), including the
 roofline of the dominant kernel (scan, HIP events on its launch stream over
-the timed region) and the CPU baseline (the oracle in reference-equivalent
-mode, timed on this host, rank 0 at N=1 only), and the parity check of the
-measured run's cuts against the oracle.
+the timed region).  A plain run sets up, warms up, times the K steps and
+prints; --dump-outputs DIR also writes the last timed step's cut lists.
+--full adds what takes time of its own: the CPU baseline (the oracle in
+reference-equivalent mode, timed on this host, rank 0 at N=1 only), the
+parity check of the measured run's cuts against the oracle, and at C3 on one
+GPU the host-to-host object (tools/ingest_e2e).
 """
 from __future__ import annotations
 
@@ -114,7 +117,47 @@ def parse():
     ap.add_argument("--abi-files", type=int, default=16)
     ap.add_argument("--e2e", action="store_true",
                     help="also measure the PCIe-inclusive rate (pinned H2D + chunk + D2H cuts)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity check of "
+                         "the measured run's cuts against the oracle, the CPU baselines, the "
+                         "host-to-host object (C3 at N=1) and C1's side measurements; each can "
+                         "still be switched off with its --no-* option")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the cut lists of the last timed step to "
+                         "DIR as .npy files (float64; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_parity = args.no_cpu_baseline = args.no_h2h = True
+    return args
+
+
+# -------------------------------------------------------------------- outputs
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, cuts_list, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step -- per stream, the end offset of every chunk -- as two float64
+    arrays (offsets stay below 2^53, so the conversion is exact):
+      cut_counts.npy  chunks per stream, in stream order
+      cuts.npy        the streams' cut offsets, concatenated in stream order
+    With more than one rank every rank writes its own pair (suffix _rank<r>).
+    Above 64 MB in all, cuts.npy holds a fixed sample instead: the entries at
+    the sorted indices drawn by numpy's default_rng(0), which depend on the
+    array's length alone."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    counts = np.array([len(c) for c in cuts_list], dtype=np.float64)
+    cuts = (np.concatenate([np.asarray(c, dtype=np.float64) for c in cuts_list])
+            if len(cuts_list) else np.zeros(0, np.float64))
+    room = (DUMP_CAP_BYTES // max(world, 1) - counts.nbytes - 4096) // 8
+    if cuts.size > room:
+        idx = np.sort(np.random.default_rng(0).choice(cuts.size, size=max(room, 0), replace=False))
+        cuts = cuts[idx]
+    np.save(os.path.join(path, f"cut_counts{sfx}.npy"), counts)
+    np.save(os.path.join(path, f"cuts{sfx}.npy"), cuts)
 
 
 # ----------------------------------------------------------------- workloads
@@ -466,6 +509,7 @@ def run_c4(args, torch, dist, dev, rank, world, local):
     sample = set(int(x) for x in rng.choice(args.c4_files, size=min(64, args.c4_files),
                                              replace=False))
     parity_acc = [0, 0, 0, 0.0]  # files diffed, mismatches, cuts diffed, seconds
+    dumped = {}  # file -> cut list of the last timed pass (--dump-outputs)
     if single and layouts:
         b, offs, plan = layouts[0]
         plan.set_timing(True, every=args.time_every)
@@ -482,6 +526,7 @@ def run_c4(args, torch, dist, dev, rank, world, local):
         plan.set_timing(False)
         runs, scan_ms, resolve_ms = plan.kernel_times()
         got = plan.results()
+        dumped.update(zip(b, got))
         ref_hashed = ref_slide_bytes(got, MIN)
         inf = plan.info()
         if inf["walk_pieces"]:
@@ -526,6 +571,8 @@ def run_c4(args, torch, dist, dev, rank, world, local):
             runs += r
             scan_ms += sm
             resolve_ms += rm
+            if args.dump_outputs and step == args.steps - 1:
+                dumped.update(zip(b, plan.results()))
             if step == 0:
                 got = plan.results()
                 ref_hashed += ref_slide_bytes(got, MIN)
@@ -548,6 +595,8 @@ def run_c4(args, torch, dist, dev, rank, world, local):
                     if f in sample and not args.no_cpu_baseline:
                         o = int(offs[i])
                         sample_cuts[f] = (got[i], arena[o:o + sizes[f]].cpu().numpy())
+    if args.dump_outputs:  # the share's cut lists in file order
+        dump_outputs(args.dump_outputs, [dumped[f] for f in sorted(dumped)], rank, world)
     t = torch.tensor([el], dtype=torch.float64, device=coll_device(dev))
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -615,6 +664,8 @@ def run_c4(args, torch, dist, dev, rank, world, local):
                        "checker": "oracle/cdc_ref on every file of every rank's share "
                                   "(untimed, after the timed passes)"},
         }
+        if not args.full:  # a plain run diffs nothing
+            del line["parity"]
         if world == 1 and not args.no_cpu_baseline and sample_cuts:
             from rustic_core_amd.device import pack_offsets
             hosts = [h for _, h in sample_cuts.values()]
@@ -670,13 +721,34 @@ def run_c1(args, torch, dev, rank, world):
             os.unlink(path)
         return el, np.cumsum(np.array(lens, dtype=np.uint64))
 
+    data = stdrng_numpy(0x256, n)
+    if not args.full:  # the headline figure alone: the drop-in path over the StdRng bytes
+        el, cuts = drop_in(data)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [cuts])
+        print(json.dumps({
+            "metric": METRIC, "value": round(n * args.steps / el / GiB, 3), "unit": "GiB/s",
+            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(el / args.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "data": "StdRng::seed_from_u64(0x256) bytes (ChaCha12, SURVEY.md 8(d)) in a file",
+            "config": {"workload": f"C1: one {n >> 20} MiB file through ChunkIter.from_config "
+                                   "(file reads + C ABI stream: H2D, device chunking, cuts D2H; "
+                                   "BASELINE.json configs[0])",
+                       "poly": hex(POLY), "min": MIN, "avg": AVG, "max": MAX},
+            "parity": {"chunks": int(len(cuts)), "mismatches": None,
+                       "checker": "none: the oracle, the device-resident rate, the CPU baseline "
+                                  "and the /dev/urandom file run under --full"},
+        }), flush=True)
+        return
     # BASELINE.json configs[0] names a /dev/urandom file: one is read here
     # beside the reproducible StdRng(0x256) stand-in
     with open("/dev/urandom", "rb") as f:
         udata = np.frombuffer(f.read(n), dtype=np.uint8)
     el_u, cuts_u = drop_in(udata)
-    data = stdrng_numpy(0x256, n)
     el, cuts = drop_in(data)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [cuts])
     # the same bytes device-resident
     ctx = Context.get(POLY, MIN, AVG, MAX, device=dev.index)
     offs, alen = pack_offsets([n])
@@ -928,6 +1000,8 @@ def main():
     scan_s = scan_ms / max(runs, 1) / 1e3
     achieved = in_bytes / scan_s / 1e9
     got_cuts = plan.results() if args.workload != "C5" else [np.asarray(plan.results()[0])]
+    if args.dump_outputs:  # C5: the rank's stitched (absolute) cuts, as the step returns them
+        dump_outputs(args.dump_outputs, [sliced.cuts(last)] if sliced else got_cuts, rank, world)
     ref_hashed = ref_slide_bytes(got_cuts, MIN)
     if walked:
         st = plan.walk_stats()

@@ -21,7 +21,7 @@ def test_bench_two_ranks_gloo(gpu_ctx):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
                         "--workload", "C2", "--steps", "2", "--warmup", "1", "--prewarm", "0",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=300,
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300,
                        env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -37,7 +37,7 @@ def _two_ranks(args, n=2):
     env = dict(os.environ, RCDC_BENCH_BACKEND="gloo")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + args +
-                       ["--warmup", "1", "--prewarm", "0", "--no-cpu-baseline"],
+                       ["--warmup", "1", "--prewarm", "0", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -46,18 +46,18 @@ case $MODE in
     run_tests ;;
   final)
     run_tests
-    timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json \
+    timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json \
       2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
     tail -c 600 $OUT/bench.json ;;
   lines)
-    timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/c3.json \
+    timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/c3.json \
       2> $OUT/c3.err || { tail $OUT/c3.err; exit 1; }
     echo c3 ok
-    timeout -k 10 200 python -u bench.py --workload C2 --steps 50 --warmup 5 > $OUT/c2.json 2> $OUT/c2.err || exit 1
-    timeout -k 10 200 python -u bench.py --workload C5 --steps 20 --warmup 5 > $OUT/c5.json 2> $OUT/c5.err || exit 1
-    timeout -k 10 200 python -u bench.py --workload C1 --steps 3 --warmup 1 > $OUT/c1.json 2> $OUT/c1.err || exit 1
+    timeout -k 10 200 python -u bench.py --workload C2 --steps 50 --warmup 5 --full > $OUT/c2.json 2> $OUT/c2.err || exit 1
+    timeout -k 10 200 python -u bench.py --workload C5 --steps 20 --warmup 5 --full > $OUT/c5.json 2> $OUT/c5.err || exit 1
+    timeout -k 10 200 python -u bench.py --workload C1 --steps 3 --warmup 1 --full > $OUT/c1.json 2> $OUT/c1.err || exit 1
     timeout -k 10 400 python -u bench.py --workload C4 --c4-files 1024 --steps 10 --warmup 3 \
-      --no-cpu-baseline > $OUT/c4.json 2> $OUT/c4.err || exit 1
+      --full --no-cpu-baseline > $OUT/c4.json 2> $OUT/c4.err || exit 1
     echo lines ok
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- \
       python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-h2h \
@@ -74,7 +74,7 @@ case $MODE in
       D=$OUT/$W; mkdir -p $D
       B=$(bench_cmd $W)
       w=$(echo $W | tr A-Z a-z)  # (tools/pmc_json.py reads $D/<w>.json)
-      timeout -k 10 400 python -u $B --steps 10 --warmup 3 > $D/$w.json 2> $D/$w.err || { tail $D/$w.err; exit 1; }
+      timeout -k 10 400 python -u $B --full --steps 10 --warmup 3 > $D/$w.json 2> $D/$w.err || { tail $D/$w.err; exit 1; }
       for c in FETCH_SIZE WRITE_SIZE; do
         timeout -s KILL 240 rocprofv3 --pmc $c -d $D/pmc_$c -o run --output-format csv -- \
           python -u $B --steps 3 --warmup 1 --prewarm 0 --no-parity > $D/pmc_$c.log 2>&1 \
