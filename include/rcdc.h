@@ -477,11 +477,19 @@ typedef struct {
  * repeat sequence tables, repeat offsets, matches into earlier blocks),
  * 1 it decodes to other bytes or another length (ErrorKind::Verification,
  * decrypt.rs:516-526), 2 malformed or not readable here (a dictionary, a
- * skippable frame, bytes after the frame).  A frame checksum is skipped.
+ * skippable frame, bytes after the frame).  A frame checksum is verified
+ * (the low 32 bits of XXH64 of the blob, once the content compared equal);
+ * a wrong one is status 2.
  * Malformed means what decode_all's decoder refuses on the path it would
  * take: one pass when the declared content size fits its first 8 KiB
  * read, otherwise the streaming stage machine (a window above 2^27 + 1
- * bytes is refused there, and empty blocks of any type are skipped).
+ * bytes is refused there, empty blocks of any type are skipped, every
+ * block's size field and regenerated bytes are bounded by
+ * min(window, 128 KiB) and every match offset by the window; the window of
+ * a single-segment frame is its content size).  On either path a
+ * compressed block has at least 3 bytes.  Where libzstd 1.4.8 is laxer
+ * than RFC 8878 (reserved mode bits, bits left in a sequences bitstream,
+ * a repeat offset resolving to 0) the RFC holds: status 2.
  * flags bit 0 (RCDC_CHECK_STORED): the "frames" are stored bytes (blobs of an
  * uncompressed repository), compared as they are.  Synchronous.  Calls on one context take turns; the context keeps a
  * 128 KiB literal scratch per resident wave (256 MiB on 256 CUs).          */

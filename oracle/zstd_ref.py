@@ -149,6 +149,35 @@ def compress(data: bytes, level: int = 3) -> bytes:
     return buf.raw[:n]
 
 
+def compress_adv(data: bytes, level: int = 3, checksum: bool = False, content_size: bool = True,
+                 window_log: Optional[int] = None) -> bytes:
+    """libzstd's advanced API (ZSTD_compress2): frames ZSTD_compress never
+    writes -- a checksum, no content size, a chosen window (blocks of the
+    window's size below 128 KiB, and a window descriptor)."""
+    L = lib()
+    sz, vp = ctypes.c_size_t, ctypes.c_void_p
+    L.ZSTD_createCCtx.restype = vp
+    L.ZSTD_freeCCtx.argtypes = [vp]
+    L.ZSTD_CCtx_setParameter.restype = sz
+    L.ZSTD_CCtx_setParameter.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    L.ZSTD_compress2.restype = sz
+    L.ZSTD_compress2.argtypes = [vp, vp, sz, vp, sz]
+    cc = L.ZSTD_createCCtx()
+    try:
+        # ZSTD_c_compressionLevel, _windowLog, _contentSizeFlag, _checksumFlag
+        params = [(100, level), (200, int(content_size)), (201, int(checksum))]
+        if window_log is not None:
+            params.append((101, window_log))
+        for p, v in params:
+            _check(L.ZSTD_CCtx_setParameter(cc, p, v))
+        cap = L.ZSTD_compressBound(len(data))
+        buf = ctypes.create_string_buffer(cap)
+        n = _check(L.ZSTD_compress2(cc, buf, cap, data, len(data)))
+        return buf.raw[:n]
+    finally:
+        L.ZSTD_freeCCtx(cc)
+
+
 def compress_into(dst_ptr: int, cap: int, src_ptr: int, n: int, level: int = 3) -> int:
     """ZSTD_compress between raw pointers (numpy buffers; for timing)."""
     return _check(lib().ZSTD_compress(dst_ptr, cap, src_ptr, n, level))

@@ -7,7 +7,11 @@ device accepts (status 0) must decode with libzstd (oracle/zstd_ref.py) to
 exactly the blob; a frame libzstd decodes to the blob must be accepted.  The
 frames come from this library's encoder and from libzstd itself at several
 levels (treeless literals, repeat-mode tables, matches into earlier blocks,
-FSE tables up to accuracy 9), plus corrupted copies of both.
+FSE tables up to accuracy 9), plus corrupted copies of both, and from
+tests/zstd_frames.py: frames built by hand for the parts of RFC 8878 no
+encoder at hand writes (window descriptors, checksums, RLE-mode tables,
+1-stream Huffman literals, every size format at its edges, blocks of any
+size), each with the verdict libzstd gives it on the CPU.
 """
 import numpy as np
 import pytest
@@ -275,3 +279,102 @@ def test_empty_compressed_block_as_decode_all(gpu_ctx):
     with pytest.raises(zr.ZstdError):
         zr.decompress_stream(small)
     assert _check(gpu_ctx, [one, small], [b"", d[:5000]]).tolist() == [2, 2]
+
+
+# ---- hand-built RFC 8878 frames (tests/zstd_frames.py) ----------------------
+# Every expectation of that table is libzstd's own verdict
+# (tests/test_zstd_host.py::test_conformance_cases_are_libzstd_verdicts), or,
+# for the few `stricter` cases, the RFC's where libzstd 1.4.8 is lax.
+
+def _wrong(cases, st):
+    return [(c.name, c.expect_status, int(s)) for c, s in zip(cases, st) if int(s) != c.expect_status]
+
+
+def test_conformance_cases(gpu_ctx):
+    """The whole table in one call, statuses exact; then reversed (another
+    queue order, another longest-first sort, other alignments).  The frames
+    and blobs sit at ragged offsets that cover every residue mod 16."""
+    from tests import zstd_frames as zf
+    for cases in (zf.CASES, zf.CASES[::-1]):
+        frames, blobs = [c.frame for c in cases], [c.blob for c in cases]
+        assert {o % 16 for o in _layout(frames, 1)[1]} == set(range(16))
+        assert {o % 16 for o in _layout(blobs, 2)[1]} == set(range(16))
+        assert _wrong(cases, _check(gpu_ctx, frames, blobs)) == []
+
+
+def test_conformance_cases_in_order_pass():
+    """The same table through the in-order pass alone (RCDC_CHECK_BLOCKS=0 is
+    read once per process: a fresh one, tools/zck_cases.py)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from tests import zstd_frames as zf
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, RCDC_CHECK_BLOCKS="0")
+    env.pop("RCDC_ZSTD_DBG", None)
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "zck_cases.py")], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    assert got["names"] == [c.name for c in zf.CASES]
+    assert _wrong(zf.CASES, got["statuses"]) == []
+
+
+def test_block_parallel_pass_settles(gpu_ctx):
+    """Frames of 2 x 128 KiB + a tail in 128 KiB blocks, the layout the
+    block-parallel pass places: valid with and without a checksum and with a
+    256 KiB window descriptor, a wrong byte in each block, an offset inside
+    and outside the window.  Which pass settled a frame cannot be seen
+    through the library's interface (rcdc_zstd_check returns statuses only,
+    and the phase counters need RCDC_ZSTD_DBG), so only the statuses are
+    asserted here; the in-order pass alone gives the same ones
+    (test_conformance_cases_in_order_pass holds these cases too)."""
+    import os
+    from tests import zstd_frames as zf
+    assert not os.environ.get("RCDC_ZSTD_DBG")
+    cases = [zf.Case(*c, None) for c in zf.BLOCK_PARALLEL]
+    assert {c.expect_status for c in cases} == {0, 1, 2}
+    st = _check(gpu_ctx, [c.frame for c in cases], [c.blob for c in cases])
+    assert _wrong(cases, st) == []
+
+
+def test_every_byte_matters(gpu_ctx):
+    """One frame of about 1.5 KiB that holds each compare path once (raw and
+    RLE blocks; raw, RLE and Huffman literals; short matches, one above 256
+    bytes, an overlapping offset-1 match, trailing literals) against its blob
+    with every single byte changed in turn, by XOR 0x01 and by XOR 0x80, the
+    blob placed at residues 0, 1, 2, 3, 5 and 15 mod 16: every one is status
+    1, the untouched blobs 0, all in one call.  A tail masked wrongly
+    (wave_cmp / lane_cmp's last 1-3 bytes, ld16u's straddle) passes a changed
+    byte here.  One call over every position at every residue takes a copy
+    of the blob per check: about 18 000 copies, 28 MiB on the device, in
+    well under a second.  Six calls, one per residue, would hold 5 MiB at a
+    time; the single call is kept because the queue then mixes residues and
+    positions among the waves."""
+    import torch
+    from rustic_core_amd.compress import check_frames
+    from tests import zstd_frames as zf
+    fr, blob = zf.EVERY_PATH
+    n = len(blob)
+    res = (0, 1, 2, 3, 5, 15)
+    stride = (n + 16 + 15) // 16 * 16
+    checks = [(r, -1, 0) for r in res] + [(r, i, x) for r in res for i in range(n) for x in (1, 0x80)]
+    darr = np.zeros(len(checks) * stride + 64, np.uint8)
+    src = np.frombuffer(blob, np.uint8)
+    doffs = []
+    for k, (r, i, x) in enumerate(checks):
+        o = k * stride + r
+        darr[o:o + n] = src
+        if i >= 0:
+            darr[o + i] ^= x
+        doffs.append(o)
+    farr, foffs = _layout([fr] * 16, 1)  # the frame at 16 ragged places
+    d_f = torch.from_numpy(farr).to("cuda:0")
+    d_d = torch.from_numpy(darr).to("cuda:0")
+    st = check_frames(gpu_ctx, d_f.data_ptr(), [foffs[k % 16] for k in range(len(checks))],
+                      [len(fr)] * len(checks), d_d.data_ptr(), doffs, [n] * len(checks))
+    torch.cuda.synchronize()
+    want = np.array([0 if i < 0 else 1 for _, i, _ in checks], np.uint32)
+    missed = [checks[k] for k in np.nonzero(st != want)[0][:20]]
+    assert missed == [], f"(residue, byte, xor) with another status: {missed}"

@@ -330,3 +330,116 @@ def test_checker_soak_verdict_helpers():
         assert S.libzstd_ok(fr, data) and not S.libzstd_ok(fr, data + b"x")
         for _ in range(20):
             S.corrupt(rng, fr, fr)  # any corruption is a byte string
+
+
+# ---- hand-built RFC 8878 frames (tests/zstd_frames.py) ----------------------
+
+def _soak():
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(__file__)), "tools"))
+    import soak_zstd_check as S
+    return S
+
+
+def test_frame_builder_constants(T):
+    """The builder restates the RFC's LL / ML code tables (it must not need
+    the library): they equal the library's, and its XXH64 is xxhash's."""
+    from tests import zstd_frames as zf
+    assert zf.T["llcode"] == [int(x) for x in T["llcode"]]
+    assert zf.T["mlcode"] == [int(x) for x in T["mlcode"]]
+    assert zf.LL_BITS == [int(x) for x in T["llbits"]]
+    assert zf.ML_BITS == [int(x) for x in T["mlbits"]]
+    for c in range(36):
+        assert zf.ll_code(zf.LL_BASE[c]) == c and zf.ll_code(zf.LL_BASE[c] + (1 << zf.LL_BITS[c]) - 1) == c
+    for c in range(53):
+        assert zf.ml_code(zf.ML_BASE[c]) == c and zf.ml_code(zf.ML_BASE[c] + (1 << zf.ML_BITS[c]) - 1) == c
+    assert zf.xxh64(b"") == 0xEF46DB3751D8E999  # the reference implementation's test vector
+    try:
+        import xxhash
+    except ImportError:
+        return
+    d = np.random.default_rng(64).integers(0, 256, 5000, dtype=np.uint8).tobytes()
+    for n in list(range(0, 100)) + [1000, 4999, 5000]:
+        assert zf.xxh64(d[:n]) == xxhash.xxh64(d[:n]).intdigest(), n
+
+
+def test_compress_adv_frames():
+    """libzstd's advanced API writes what ZSTD_compress never does: a
+    checksum, no content size, a window descriptor with blocks of 1 KiB."""
+    d = bytes(range(256)) * 40
+    plain = zr.compress(d, 3)
+    assert plain[4] & 0x24 == 0x20  # single-segment, no checksum
+    ck = zr.compress_adv(d, 3, checksum=True)
+    assert ck[4] & 4 and len(ck) == len(plain) + 4 and zr.decompress_stream(ck) == d
+    nc = zr.compress_adv(d, 3, content_size=False)
+    assert nc[4] >> 6 == 0 and not nc[4] & 0x20 and zr.content_size(nc) is None
+    assert zr.decompress_stream(nc) == d
+    w10 = zr.compress_adv(d, 3, window_log=10)
+    assert not w10[4] & 0x20 and w10[5] == 0 and zr.decompress_stream(w10) == d
+    heads, _ = _soak().block_spots(w10)
+    assert len(heads) == len(d) // 1024
+
+
+def test_conformance_cases_are_libzstd_verdicts():
+    """Every case of tests/zstd_frames.py, judged by this machine's libzstd
+    alone, the way the soak does (decode_all's streaming decoder, the frame
+    exactly its bytes, no reserved mode bits): the verdict is the case's
+    expectation.  The cases marked `stricter` are the rules where the checker
+    follows RFC 8878 and libzstd 1.4.8 is lax: there libzstd accepts the
+    frame and decodes it to the blob (only in that direction: a frame the
+    checker accepts is never excepted)."""
+    from tests import zstd_frames as zf
+    S = _soak()
+    old = tuple(int(x) for x in zr.version().split(".")) < (1, 5)
+    names = [c.name for c in zf.CASES]
+    assert len(set(names)) == len(names) > 250
+    assert sum(c.expect_status == 0 for c in zf.CASES) > 100
+    assert sum(c.expect_status == 1 for c in zf.CASES) > 30
+    assert sum(c.expect_status == 2 for c in zf.CASES) > 60
+    wrong = []
+    for c in zf.CASES:
+        if c.stricter is None:
+            if S.libzstd_ok(c.frame, c.blob) != (c.expect_status == 0):
+                wrong.append(c.name)
+            continue
+        assert c.expect_status == 2 and isinstance(c.stricter, str) and c.stricter[0].isdigit(), c.name
+        if old:
+            try:
+                lax = zr.frame_size(c.frame) == len(c.frame) and zr.decompress_stream(c.frame) == c.blob
+            except zr.ZstdError:
+                lax = False
+            if not lax:
+                wrong.append(c.name)
+    assert wrong == []
+    assert sorted(c.name for c in zf.CASES if c.stricter) == [
+        "an unread zero byte below the sequences bitstream", "repeat offset resolving to 0",
+        "reserved bits of the modes byte"]
+
+
+def test_conformance_case_structure():
+    """The builder decides the structure: the frames that claim a feature
+    carry it (frame header fields as libzstd parses them, block types, and
+    the one-pass / streamed split of kernel and decoder)."""
+    from tests import zstd_frames as zf
+    by = {c.name: c for c in zf.CASES}
+    for fb in (1, 2, 4, 8):
+        fr = by[f"hdr single fcs{fb}"].frame
+        assert fr[4] >> 6 == {1: 0, 2: 1, 4: 2, 8: 3}[fb] and fr[4] & 0x20
+        assert zr.content_size(fr) == len(by[f"hdr single fcs{fb}"].blob)
+    assert zr.content_size(by["hdr window 1K fcs0"].frame) is None
+    assert by["hdr window 2^27 no fcs"].frame[5] == 17 << 3
+    assert by["hdr window 2^27+2^24 no fcs"].frame[5] == (17 << 3) + 1
+    for name in ("checksum raw", "checksum rle", "checksum compressed", "libzstd advanced: checksum"):
+        assert by[name].frame[4] & 4, name
+        assert by[name].frame[-4:] == (zf.xxh64(by[name].blob) & 0xFFFFFFFF).to_bytes(4, "little")
+    S = _soak()
+    heads, bodies = S.block_spots(by["libzstd advanced: windowLog 10"].frame)
+    assert len(heads) >= 190 and bodies  # blocks of 1 KiB, compressed ones among them
+    fr, blob = zf.EVERY_PATH
+    heads, bodies = S.block_spots(fr)
+    assert [(int.from_bytes(fr[h:h + 3], "little") >> 1) & 3 for h in heads] == [0, 1, 2, 2, 2]
+    assert [fr[b] & 3 for b in bodies] == [0, 1, 2]  # raw, RLE, Huffman literals
+    # the block-parallel cases: blocks of 128 KiB and a tail
+    for name, fr, blob, st in zf.BLOCK_PARALLEL:
+        assert len(blob) > 2 * zf.BLOCK
