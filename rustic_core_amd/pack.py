@@ -15,12 +15,12 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
-from .errors import status_error
+from .errors import ErrorKind, RusticError, status_error
 
 MB = 1 << 20
 MAX_SIZE = 4076 * MB   # packer.rs:58
@@ -82,6 +82,52 @@ class PackSizer:
 def header_entry_len(uncompressed_len: int) -> int:
     """HeaderEntry::length (packfile.rs:158-163): 37, or 41 compressed."""
     return 41 if uncompressed_len else 37
+
+
+class HeaderBlob(NamedTuple):
+    """A pack header entry as PackHeader::from_binary gives it
+    (packfile.rs:228-242): an IndexBlob with its running offset."""
+    type: int              # BlobType: 0 data, 1 tree
+    offset: int            # of the sealed blob in the pack
+    length: int            # sealed length
+    uncompressed_len: int  # 0: stored (``None`` in the reference)
+    id: bytes
+
+
+def parse_header(header: bytes) -> List[HeaderBlob]:
+    """PackHeader::from_binary over an opened (decrypted) pack header: the
+    inverse of the HeaderEntry layout rcdc_pack_build writes
+    (packfile.rs:88-124): type byte 0 data / 1 tree, then u32 length and the
+    32-byte id (37 bytes); 2 compressed data / 3 compressed tree, then u32
+    length, u32 uncompressed length and the id (41 bytes).  Offsets run from
+    0 in header order.  A type byte above 3 or an entry cut short is
+    ErrorKind.Internal ("Error reading pack header", check.rs:768-777)."""
+    header = bytes(header)
+    out, pos, off = [], 0, 0
+    while pos < len(header):
+        t = header[pos]
+        if t > 3:
+            raise RusticError(ErrorKind.Internal,
+                              f"Error reading pack header: unknown entry type {t} at byte {pos}")
+        size = 41 if t >= 2 else 37
+        if pos + size > len(header):
+            raise RusticError(ErrorKind.Internal,
+                              f"Error reading pack header: entry at byte {pos} is cut short "
+                              f"({len(header) - pos} of {size} bytes)")
+        length = int.from_bytes(header[pos + 1:pos + 5], "little")
+        ulen = int.from_bytes(header[pos + 5:pos + 9], "little") if t >= 2 else 0
+        out.append(HeaderBlob(t & 1, off, length, ulen, header[pos + size - 32:pos + size]))
+        off += length
+        pos += size
+    return out
+
+
+def header_size(entries) -> int:
+    """Bytes of the plain header of these entries (HeaderBlob or IndexBlob):
+    the sum of HeaderEntry::length.  PackHeaderRef::size (packfile.rs:368-372)
+    and the u32 at the pack's end are this plus the 32 bytes of sealing."""
+    return sum(header_entry_len(getattr(e, "uncompressed_len", None) or
+                                getattr(e, "uncompressed_length", None) or 0) for e in entries)
 
 
 def group_blobs(lens: Sequence[int], sizer: PackSizer,
