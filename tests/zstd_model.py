@@ -260,6 +260,9 @@ def huf_literals_section(lits: bytes):
         streams.append(bytes(bw.out))
     jump = b"".join(len(s).to_bytes(2, "little") for s in streams[:3])
     comp = len(tree) + 6 + sum(len(s) for s in streams)
+    hl = 3 if n < 1024 else 4 if n < 16384 else 5
+    if hl + comp >= (1 if n < 32 else 2 if n < 4096 else 3) + n:  # no gain over raw
+        return None
     if n < 1024:
         hdr = (2 | 1 << 2 | n << 4 | comp << 14).to_bytes(3, "little")
     elif n < 16384:
@@ -267,6 +270,45 @@ def huf_literals_section(lits: bytes):
     else:
         hdr = (2 | 3 << 2 | n << 4 | comp << 22).to_bytes(5, "little")
     return hdr + tree + jump + b"".join(streams)
+
+
+def raw_literals_section(lits: bytes, ltype=0):
+    n = len(lits)
+    body = bytes(lits) if ltype == 0 else bytes(lits[:1])
+    if n < 32:
+        return bytes([ltype | n << 3]) + body
+    if n < 4096:
+        return (ltype | 1 << 2 | n << 4).to_bytes(2, "little") + body
+    return (ltype | 3 << 2 | n << 4).to_bytes(3, "little") + body
+
+
+def huf_gate_costs(lits: bytes):
+    """The device's order-0 entropy gate before any Huffman work
+    (encode_literals: hbits * 0.125 + 64 < nl), as two costs in bits: the
+    Huffman estimate (entropy + 64 bytes) and the raw bytes.  Huffman is tried
+    when the first is below the second."""
+    import math
+    n = len(lits)
+    counts = np.bincount(np.frombuffer(lits, np.uint8), minlength=256)
+    hbits = sum(int(c) * math.log2(n / int(c)) for c in counts if c)
+    return hbits + 512.0, 8.0 * n
+
+
+def literals_section(lits: bytes, force_huf=None):
+    """The literals section as the device's encode_literals writes it: from
+    64 literals up, RLE for a single byte value; Huffman when the entropy
+    gate lets it try (force_huf overrides the gate alone) and the section
+    comes out smaller than raw; raw otherwise."""
+    lits = bytes(lits)
+    if len(lits) >= 64:
+        if len(set(lits)) == 1:
+            return raw_literals_section(lits, 1)
+        a, b = huf_gate_costs(lits)
+        if (a < b) if force_huf is None else force_huf:
+            sec = huf_literals_section(lits)
+            if sec is not None:
+                return sec
+    return raw_literals_section(lits)
 
 
 def compressed_block_huf(T, data: bytes, seqs):
@@ -455,10 +497,18 @@ def _cost_bits(counts, norm, tl):
     return sum(c * (tl - math.log2(norm[s])) for s, c in enumerate(counts) if c)
 
 
-def sequences_section_adaptive(T, seqs, values=False):
+def sequence_table_costs(T, seqs, values=False):
+    """{stream: (predefined bits, adaptive bits with its description)} as
+    sequences_section_adaptive weighs them."""
+    return sequences_section_adaptive(T, seqs, values, costs=True)
+
+
+def sequences_section_adaptive(T, seqs, values=False, force=None, costs=False):
     """Sequences section choosing, per stream, predefined or an adaptive
-    log-6 table by estimated bits (the device's rule)."""
+    log-6 table by estimated bits (the device's rule).  force: {stream: mode
+    0 or 2} overrides a stream's choice; costs: return the estimates."""
     k = len(seqs)
+    force, est = force or {}, {}
     codes = [_codes(T, *s, values) for s in seqs]
     hist = {"ll": [0] * 36, "ml": [0] * 53, "of": [0] * 32}
     for llc, mlc, ofc, _, _ in codes:
@@ -478,7 +528,8 @@ def sequences_section_adaptive(T, seqs, values=False):
         last = max(s for s in range(len(cnt)) if cnt[s])
         desc = fse_write_ncount(an[:last + 1], FSE_ADAPT_LOG)
         acost = _cost_bits(cnt, an, FSE_ADAPT_LOG) + 8 * len(desc)
-        if acost < pcost:
+        est[name] = (pcost, acost)
+        if (acost < pcost) if name not in force else force[name] == 2:
             modes[name], descs[name] = 2, desc
             tt, st = fse_ctable(an[:last + 1], FSE_ADAPT_LOG)
             tabs[name] = (tt, st, FSE_ADAPT_LOG)
@@ -486,6 +537,8 @@ def sequences_section_adaptive(T, seqs, values=False):
             modes[name], descs[name] = 0, b""
             tt, st = fse_ctable(pn, ptl)
             tabs[name] = (tt, st, ptl)
+    if costs:
+        return est
     if k < 128:
         sh = bytes([k])
     elif k < 0x7F00:
@@ -497,29 +550,42 @@ def sequences_section_adaptive(T, seqs, values=False):
                                                                                values)
 
 
-def compressed_block_adaptive(T, data: bytes, seqs, reps=False):
-    """Huffman literals (where they apply) + adaptive sequences; reps: code
-    offsets with block-local repeat codes (offsets_to_values)."""
+def block_literals(data: bytes, seqs):
     lits = bytearray()
     pos = 0
-    for ll, ml, off in seqs:
+    for ll, ml, _ in seqs:
         lits += data[pos:pos + ll]
         pos += ll + ml
     lits += data[pos:]
-    sec = huf_literals_section(bytes(lits))
-    if sec is None:
-        n = len(lits)
-        if n < 32:
-            sec = bytes([n << 3]) + bytes(lits)
-        elif n < 4096:
-            sec = (1 << 2 | n << 4).to_bytes(2, "little") + bytes(lits)
-        else:
-            sec = (3 << 2 | n << 4).to_bytes(3, "little") + bytes(lits)
+    return bytes(lits)
+
+
+def compressed_block_adaptive(T, data: bytes, seqs, reps=False, values=False, force=None):
+    """The device's compressed block: literals_section + adaptive sequences.
+    reps: code offsets with block-local repeat codes (offsets_to_values);
+    values: seqs already carry offset values; force: {"huf": bool, "ll" /
+    "of" / "ml": 0 or 2} overrides single decisions (block_decisions)."""
+    force = force or {}
+    sec = literals_section(block_literals(data, seqs), force.get("huf"))
     if not seqs:
         return sec + b"\x00"
     if reps:
-        return sec + sequences_section_adaptive(T, offsets_to_values(seqs), True)
-    return sec + sequences_section_adaptive(T, seqs)
+        seqs, values = offsets_to_values(seqs), True
+    return sec + sequences_section_adaptive(T, seqs, values, force)
+
+
+def block_decisions(T, data: bytes, seqs, values=False):
+    """{decision: (cost of the first choice, cost of the second)} in bits for
+    every estimate-driven choice of compressed_block_adaptive: "huf" (try
+    Huffman, or raw) from 64 literals of two values up, and per stream
+    predefined or adaptive."""
+    lits = block_literals(data, seqs)
+    out = {}
+    if len(lits) >= 64 and len(set(lits)) > 1:
+        out["huf"] = huf_gate_costs(lits)
+    if seqs:
+        out.update(sequence_table_costs(T, seqs, values))
+    return out
 
 
 # ---- FSE-compressed Huffman weights (RFC 8878 4.2.1.2), for maxsym > 128 ---

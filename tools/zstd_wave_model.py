@@ -26,11 +26,19 @@ def zhash(k, hl):
     return ((k * 0x9E3779B97F4A7C15) & M64) >> (64 - hl)
 
 
+def ztag(k):
+    return ((k * 0xC2B2AE3D27D4EB4F) & M64) >> 49
+
+
 def parse(blk, hl=12, key=6, repchk=True, rep1=True, insall=False, ins_sel=True, lazy_rep=True,
-          phases=1, rep2=False, ins_end=False, rep_longer=False):
+          phases=1, rep2=False, ins_end=False, rep_longer=False, wide=False):
+    """wide: the levels <= 2 table (rcdc_zstd_block_kernel<11, false>): 2^hl
+    entries of a 17-bit position and a 15-bit tag of the key; a candidate
+    only when the tag agrees, at any distance inside the block."""
     n = len(blk)
     b = np.frombuffer(blk, np.uint8)
     tab = [None] * (1 << hl)
+    tags = [None] * (1 << hl)
     anchor, base, ilimit = 0, 0, n - 8
     r0 = r1 = r2 = 0
     seqs = []
@@ -71,7 +79,10 @@ def parse(blk, hl=12, key=6, repchk=True, rep1=True, insall=False, ins_sel=True,
                         tab[H[q]] = P[q] & 0xFFFF
             e = tab[h]
             c = None
-            if e is not None:
+            if wide:
+                if e is not None and tags[h] == ztag(k):
+                    c = e
+            elif e is not None:
                 c = (p & ~0xFFFF) | e
                 if c >= p:
                     c = c - 0x10000 if c >= 0x10000 else None
@@ -150,11 +161,72 @@ def parse(blk, hl=12, key=6, repchk=True, rep1=True, insall=False, ins_sel=True,
                 ends.append((zhash(int.from_bytes(blk[q:q + key], "little"), hl), q))
         for l in range(64):
             if act[l] and (insall or not covered[l] or (ins_sel and l in sel)):
-                tab[H[l]] = P[l] & 0xFFFF
+                if wide:
+                    tab[H[l]] = P[l]
+                    tags[H[l]] = ztag(int.from_bytes(blk[P[l]:P[l] + key], "little"))
+                else:
+                    tab[H[l]] = P[l] & 0xFFFF
         for h, q in ends:
             tab[h] = q & 0xFFFF
         base = max(base + 64 * stride, anchor)
     return seqs
+
+
+def level_params(level, blk):
+    """parse()'s options for a level as rcdc_zstd.hip zstd_strategy sets them
+    (defaults, no RCDC_ZSTD_* overrides), with the block's own key length:
+    narrow tables key on 5 bytes unless >= 10 % of the four sampled 1 KiB
+    windows are ASCII digits (blocks of 8 KiB and more; 6 below)."""
+    level = level or 3
+    kw = dict(repchk=True, rep1=True, rep2=True, lazy_rep=False)
+    if level <= 2:
+        return dict(kw, hl=11, wide=True, key=6 if level <= 1 else 4)
+    key, n = 6, len(blk)
+    if n >= 8192:
+        digits = sum(sum(48 <= x <= 57 for x in blk[((n // 4) * w & ~15):((n // 4) * w & ~15) + 1024])
+                     for w in range(4))
+        key = 5 if digits * 10 < 4096 else 6
+    return dict(kw, hl=13 if level >= 4 else 12, key=key)
+
+
+def _entropy_bits(sample):
+    import math
+    cnt = np.bincount(np.frombuffer(sample, np.uint8), minlength=256)
+    return sum(int(c) * math.log2(len(sample) / int(c)) for c in cnt if c)
+
+
+def block_model(blk, level, first):
+    """(type, content) of one block as rcdc_zstd_block_kernel decides it,
+    far candidates aside: raw below 16 bytes, RLE (the frame's first block:
+    one literal and an offset-1 match), raw on the two entropy samples, the
+    wave parse, zstd_model's block coder and the keep rule."""
+    from tests.zstd_frames import T
+    n = len(blk)
+    if n < 16:
+        return 0, blk
+    if len(set(blk)) == 1:
+        if not first:
+            return 1, blk[:1]
+        vals = [(1, n - 1, 4)]
+    else:
+        if n >= 8192:
+            s = b"".join(blk[((n // 4) * w & ~15):((n // 4) * w & ~15) + 1024] for w in range(4))
+            if _entropy_bits(s) > 7.9 * 4096:
+                return 0, blk
+        vals = zm.offsets_to_values(parse(blk, **level_params(level, blk)))
+        if not vals and _entropy_bits(blk[:min(n, 4096) & ~15]) > 7.5 * (min(n, 4096) & ~15):
+            return 0, blk
+    out = zm.compressed_block_adaptive(T, blk, vals, values=True)
+    return (2, out) if len(out) < n - (n >> 6) - 2 else (0, blk)
+
+
+def device_frame(data, level):
+    """The frame the device writes for a blob of up to 128 MiB, as far as
+    this model goes (no far candidates: blocks after the first may differ at
+    levels >= 3)."""
+    bs = 128 << 10
+    blocks = [block_model(data[o:o + bs], level, o == 0) for o in range(0, max(len(data), 1), bs)]
+    return zm.frame([(t, c, min(bs, len(data) - i * bs)) for i, (t, c) in enumerate(blocks)], len(data))
 
 
 def size(data, bs=128 << 10, **kw):
