@@ -498,6 +498,51 @@ rcdc_status rcdc_zstd_check(rcdc_ctx *ctx, const void *d_frames, const void *d_d
                             uint32_t *status, void *hip_stream);
 #define RCDC_CHECK_STORED 1u
 
+/* ---- zstd frames decompressed on the device: the read direction
+ * (read_encrypted_from_partial, decrypt.rs:71-97; check_pack,
+ * check.rs:718-814).  Additive entry points of ABI 5. ---------------------- */
+
+/* Frame [frame_off, frame_off + frame_len) of d_frames decodes into
+ * [out_off, out_off + out_cap) of d_out. */
+typedef struct {
+    uint64_t frame_off;
+    uint64_t frame_len;
+    uint64_t out_off;
+    uint64_t out_cap;
+} rcdc_zstd_dec_ref;  /* 32 B */
+
+/* decode_all (decrypt.rs:78) for n frames in HBM.  refs, out_lens, status: HOST arrays.
+ * status[i]: 0 decoded, out_lens[i] bytes written at out_off; 1 valid so far but the
+ * output does not fit out_cap; 2 malformed or not readable here -- exactly the rules
+ * of rcdc_zstd_check's status 2 (a frame that is malformed anywhere is 2, also when
+ * its output would not fit).  Nothing outside [out_off, out_off + out_cap) is
+ * ever written; on a non-zero status the bytes inside are unspecified.  Any alignment
+ * (allow 4 readable bytes after the frames and the output).  flags: 0.
+ * Synchronous; calls on one context take turns.  The context keeps a workspace of
+ * the frames' literals and 8 bytes per sequence, at most 4 GiB at a time
+ * (RCDC_ZDX_WS_MAX, bytes, overrides; frames that need more run in groups).
+ * RCDC_ZDX_BLOCKS=0 decodes every frame's entropy in order (A/B). */
+rcdc_status rcdc_zstd_decompress(rcdc_ctx *ctx, const void *d_frames, const rcdc_zstd_dec_ref *refs,
+                                 uint32_t n, uint32_t flags, void *d_out,
+                                 uint64_t *out_lens, uint32_t *status, void *hip_stream);
+
+/* Host only (frame in host memory, no device): declared content size (UINT64_MAX if the
+ * header has none), an upper bound of the decoded size from the block headers
+ * (128 KiB per compressed block, exact for raw/RLE), and the block count, of the
+ * first frame in [frame, frame + len).  RCDC_ERR_INVALID_INPUT for what the header
+ * walk refuses: another magic, the reserved bit, a dictionary, a reserved block
+ * type, a header or block past the end. */
+rcdc_status rcdc_zstd_frame_info(const uint8_t *frame, uint64_t len, uint64_t *content_size,
+                                 uint64_t *out_bound, uint32_t *nblocks);
+
+/* Counters of the context's last rcdc_zstd_decompress call: [0] frames, [1] compressed
+ * blocks decoded by the parallel pass, [2] compressed blocks decoded by the in-order
+ * entropy pass, [3] treeless blocks resolved from an earlier block in the parallel
+ * pass, [4] workspace groups, [5] peak workspace bytes; [6], [7] zero, or with
+ * RCDC_ZDX_TIME=1 the microseconds of the entropy kernels and of the copy kernel
+ * (HIP events, a synchronisation per group: for measuring). */
+rcdc_status rcdc_zstd_decompress_stats(rcdc_ctx *ctx, uint64_t out[8]);
+
 /* The FSE coding tables the kernels use (predefined distributions, RFC 8878
  * 3.1.1.3.2.2), copied to out (rcdc_zstd_tables_size() bytes): for tests. */
 void rcdc_zstd_tables(void *out);

@@ -39,6 +39,7 @@ EXPORTS = (
     "rcdc_ingest_stream_reserve", "rcdc_ingest_stream_close", "rcdc_ingest_stream_abort",
     "rcdc_ingest_footprint", "rcdc_ingest_mem_live", "rcdc_index_create", "rcdc_index_destroy",
     "rcdc_index_add", "rcdc_index_size", "rcdc_ingest_set_index",
+    "rcdc_zstd_decompress", "rcdc_zstd_frame_info", "rcdc_zstd_decompress_stats",
 )
 ABI_VERSION = 5
 
@@ -185,6 +186,12 @@ def lib() -> ctypes.CDLL:
     L.rcdc_zstd_compress.argtypes = [vp, ctypes.c_int, vp, vp, u32, vp, vp, vp]
     L.rcdc_zstd_check.restype = st
     L.rcdc_zstd_check.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
+    L.rcdc_zstd_decompress.restype = st
+    L.rcdc_zstd_decompress.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
+    L.rcdc_zstd_frame_info.restype = st
+    L.rcdc_zstd_frame_info.argtypes = [vp, u64, P(u64), P(u64), P(u32)]
+    L.rcdc_zstd_decompress_stats.restype = st
+    L.rcdc_zstd_decompress_stats.argtypes = [vp, vp]
     L.rcdc_zstd_tables.restype = None
     L.rcdc_zstd_tables.argtypes = [vp]
     L.rcdc_zstd_tables_size.restype = u64

@@ -102,6 +102,99 @@ def check_frames(ctx: Context, d_frames: int, frame_offs, frame_lens, d_data: in
     return status[:n]
 
 
+# rcdc_zstd_dec_ref (include/rcdc.h)
+ZSTD_DEC_REF = np.dtype([("frame_off", "<u8"), ("frame_len", "<u8"), ("out_off", "<u8"),
+                         ("out_cap", "<u8")])
+assert ZSTD_DEC_REF.itemsize == 32
+
+
+class ZstdDecRef(ctypes.Structure):
+    """rcdc_zstd_dec_ref as ctypes sees it."""
+    _fields_ = [("frame_off", ctypes.c_uint64), ("frame_len", ctypes.c_uint64),
+                ("out_off", ctypes.c_uint64), ("out_cap", ctypes.c_uint64)]
+
+
+# frame decompression status (rcdc_zstd_decompress)
+DEC_OK, DEC_FULL, DEC_CORRUPT = 0, 1, 2
+
+DECODE_MESSAGE = "Failed to decode zstd compressed data. The data may be corrupted."  # decrypt.rs:79
+# the counters of rcdc_zstd_decompress_stats, in order
+DEC_STATS = ("frames", "blocks_parallel", "blocks_in_order", "treeless_resolved", "groups",
+             "workspace_bytes", "entropy_us", "copy_us")
+
+
+def decompress_frames(ctx: Context, d_frames: int, frame_offs, frame_lens, d_out: int, out_offs,
+                      out_caps, hip_stream: Optional[int] = None):
+    """decode_all (decrypt.rs:78) of every frame on the device
+    (rcdc_zstd_decompress): frame i is written to [out_offs[i], out_offs[i] +
+    out_caps[i]) of d_out.  Returns (status, out_lens): 0 = decoded,
+    out_lens[i] bytes; 1 = the output does not fit out_caps[i]; 2 = malformed
+    or not readable here.  Nothing outside a frame's output range is written."""
+    n = len(frame_lens)
+    refs = np.zeros(max(n, 1), ZSTD_DEC_REF)
+    refs["frame_off"][:n] = np.asarray(frame_offs, np.uint64)
+    refs["frame_len"][:n] = np.asarray(frame_lens, np.uint64)
+    refs["out_off"][:n] = np.asarray(out_offs, np.uint64)
+    refs["out_cap"][:n] = np.asarray(out_caps, np.uint64)
+    status = np.zeros(max(n, 1), np.uint32)
+    out_lens = np.zeros(max(n, 1), np.uint64)
+    st = _lib.lib().rcdc_zstd_decompress(ctx.handle, ctypes.c_void_p(d_frames), refs.ctypes.data, n,
+                                         0, ctypes.c_void_p(d_out), out_lens.ctypes.data,
+                                         status.ctypes.data, ctypes.c_void_p(hip_stream or 0))
+    if st:
+        raise status_error(st, _lib.last_error())
+    return status[:n], out_lens[:n]
+
+
+def decompress_stats(ctx: Context) -> dict:
+    """The counters of the context's last decompress_frames call (DEC_STATS)."""
+    out = np.zeros(8, np.uint64)
+    st = _lib.lib().rcdc_zstd_decompress_stats(ctx.handle, out.ctypes.data)
+    if st:
+        raise status_error(st, _lib.last_error())
+    return {k: int(v) for k, v in zip(DEC_STATS, out)}
+
+
+def frame_info(frame: bytes):
+    """(content size or None, upper bound of the decoded size, block count)
+    of the first frame in ``frame``, from its headers alone, on the host
+    (rcdc_zstd_frame_info).  Raises ErrorKind.InvalidInput for what the header
+    walk refuses."""
+    frame = bytes(frame)
+    cs, bound, nb = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    buf = (ctypes.c_uint8 * max(len(frame), 1)).from_buffer_copy(frame or b"\0")
+    st = _lib.lib().rcdc_zstd_frame_info(ctypes.cast(buf, ctypes.c_void_p), len(frame),
+                                         ctypes.byref(cs), ctypes.byref(bound), ctypes.byref(nb))
+    if st:
+        raise status_error(st, _lib.last_error())
+    return (None if cs.value == (1 << 64) - 1 else int(cs.value)), int(bound.value), int(nb.value)
+
+
+def decode_all(frame: bytes, device: int = 0) -> bytes:
+    """zstd::decode_all for one frame, through HBM (decrypt.rs:78).  The
+    output's capacity comes from the frame's headers (frame_info).  A frame
+    that does not decode raises ErrorKind.Internal with the reference's
+    message."""
+    import torch
+    try:
+        cs, bound, _ = frame_info(frame)
+    except RusticError as e:
+        raise RusticError(ErrorKind.Internal, DECODE_MESSAGE) from e
+    cap = bound if cs is None else cs
+    dev = torch.device("cuda", device)
+    src = torch.zeros(len(frame) + 4, dtype=torch.uint8)
+    src[:len(frame)] = torch.frombuffer(bytearray(frame), dtype=torch.uint8)
+    d_in = src.to(dev)
+    d_out = torch.empty(cap + 4, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev).cuda_stream
+        st, ln = decompress_frames(_ctx(device), d_in.data_ptr(), [0], [len(frame)],
+                                   d_out.data_ptr(), [0], [cap], s)
+    if int(st[0]) != DEC_OK:
+        raise RusticError(ErrorKind.Internal, DECODE_MESSAGE)
+    return d_out[:int(ln[0])].cpu().numpy().tobytes()
+
+
 VERIFY_MESSAGE = ("Verification failed: After decrypting and decompressing the data changed! "
                   "The data may be corrupted.")  # decrypt.rs:519-521
 

@@ -314,4 +314,70 @@ struct ZstdTables {
 };
 static_assert(sizeof(ZstdTables) % 4 == 0, "ZstdTables is copied as words");
 
+// ---- frame decompression (rcdc_zstd_dx.hip) --------------------------------
+// rcdc_zdx_blocks_kernel walks every frame's headers twice: first to count
+// (ZdxFrame: blocks and workspace bytes, read back by the host, which lays
+// the workspace out), then to write one ZdxBlk per block at the place the
+// host gave the frame (ZdxPlace).  The entropy kernels fill a compressed
+// block's slot of the data region -- its literals, then one 8-byte record per
+// sequence -- and its ZdxRes; rcdc_zdx_copy_kernel executes them into d_out.
+constexpr uint32_t kZdxInOrder = 1;   // ZdxFrame.flags: needs the in-order entropy pass
+constexpr uint32_t kZdxHasFcs = 2;    //   the header declares a content size
+constexpr uint32_t kZdxChecksum = 4;  //   a Content_Checksum follows the last block
+constexpr uint32_t kZdxNoTree = 0xFFFFFFFFu;
+// a sequence record: literal length | (match length - 3) << 17 | offset value
+// << 34 (the value before repeat-offset resolution, clamped to 30 bits: no
+// frame this decoder accepts reaches back 2^30 bytes)
+constexpr uint32_t kZdxRecMlShift = 17, kZdxRecOfShift = 34;
+constexpr uint32_t kZdxOfvMax = (1u << 30) - 1u;
+
+struct ZdxFrame {  // 48 B
+    uint64_t fcs;        // declared content size (kZdxHasFcs)
+    uint64_t need;       // data-region bytes: sum of (literals rounded up to 16 + 8 nseq)
+    uint32_t nblk;       // blocks
+    uint32_t ncomp;      // of them compressed (and not empty)
+    uint32_t ntreeless;  // treeless literals sections that have an earlier tree
+    uint32_t flags;      // kZdx*
+    uint32_t status;     // 0, 1 (declared size above out_cap) or 2
+    uint32_t wlim;       // largest match offset (~0u: decode_all's one-pass path)
+    uint32_t bmax;       // Block_Maximum_Size
+    uint32_t pad;
+};
+static_assert(sizeof(ZdxFrame) == 48, "ZdxFrame is 48 B");
+
+struct ZdxPlace {  // host -> device, per frame
+    uint64_t blk0;   // its first ZdxBlk / ZdxRes slot
+    uint64_t data0;  // its first byte of the data region
+};
+
+struct ZdxBlk {  // 48 B
+    uint64_t content;  // block content: offset in the frames buffer
+    uint64_t lit_off;  // data region: the decoded literals (8-aligned)
+    uint64_t seq_off;  // data region: the sequence records
+    uint32_t size;     // Block_Size field
+    uint32_t type;     // 0 raw, 1 RLE, 2 compressed
+    uint32_t regen;    // literals: regenerated size
+    uint32_t nseq;
+    uint32_t tree;     // treeless literals: the slot of the block whose tree they use
+    uint32_t frame;
+};
+static_assert(sizeof(ZdxBlk) == 48, "ZdxBlk is 48 B");
+
+struct ZdxRes {  // 16 B, per compressed block, from the entropy kernels
+    uint32_t status;    // 0 or 2
+    uint32_t lit_used;  // sum of the literal lengths
+    uint32_t regen;     // bytes the block regenerates
+    uint32_t pad;
+};
+
+// Every region of the decompressor's workspace (one allocation): offsets and
+// capacities in bytes.  The host computes it; the allocation's size and every
+// kernel index derive from it.
+struct ZdxLayout {
+    uint64_t blk_off, blk_cap;    // ZdxBlk[]
+    uint64_t res_off, res_cap;    // ZdxRes[]
+    uint64_t data_off, data_cap;  // literals and sequence records
+    uint64_t total;
+};
+
 }  // namespace rcdc

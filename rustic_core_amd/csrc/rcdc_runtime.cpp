@@ -92,6 +92,20 @@ hipError_t launch_zstd_check_blocks(const uint8_t *frames, const uint8_t *data, 
                                     const uint64_t *blk0, uint32_t n, void *blks, uint64_t nblk,
                                     uint8_t *scratch, uint32_t grid, uint32_t *status,
                                     uint32_t *ctr, hipStream_t stream);
+uint32_t zdx_waves_per_cu();
+hipError_t launch_zdx_blocks(const uint8_t *frames, const void *refs, uint32_t n, bool write,
+                             bool all_in_order, const ZdxPlace *place, const ZdxLayout &lay,
+                             uint8_t *ws, ZdxFrame *frm, hipStream_t stream);
+hipError_t launch_zdx_entropy(const uint8_t *frames, const ZdxFrame *frm, const ZdxLayout &lay,
+                              uint8_t *ws, uint64_t nblk, uint32_t grid, uint32_t *ctr,
+                              hipStream_t stream);
+hipError_t launch_zdx_inorder(const uint8_t *frames, const ZdxFrame *frm, const ZdxPlace *place,
+                              const uint32_t *list, uint32_t nlist, const ZdxLayout &lay, uint8_t *ws,
+                              uint32_t grid, uint32_t *ctr, hipStream_t stream);
+hipError_t launch_zdx_copy(const uint8_t *frames, const void *refs, const ZdxFrame *frm,
+                           const ZdxPlace *place, const uint32_t *order, uint32_t nlist,
+                           const ZdxLayout &lay, uint8_t *ws, uint8_t *d_out, uint64_t *out_lens,
+                           uint32_t *status, uint32_t grid, uint32_t *ctr, hipStream_t stream);
 hipError_t launch_plan_set_len(StreamDesc *sds, ScanItem *items, uint32_t nitems, uint64_t n,
                                uint64_t nseg, hipStream_t stream);
 hipError_t launch_copy_ranges(uint8_t *out, const void *units, uint32_t n, uint32_t cus,
@@ -356,6 +370,16 @@ struct rcdc_ctx {
     uint64_t *d_zck_blk0 = nullptr;  // block-parallel pass: per-frame block slots
     uint8_t *d_zck_blks = nullptr;
     uint64_t cap_zck_blk0 = 0, cap_zck_blks = 0;
+    // frame decompression (rcdc_zstd_decompress): calls on one context take turns
+    std::mutex zdx_mu;
+    uint64_t *d_zdx_refs = nullptr, *d_zdx_lens = nullptr;
+    ZdxFrame *d_zdx_frm = nullptr;
+    ZdxPlace *d_zdx_place = nullptr;
+    uint32_t *d_zdx_order = nullptr, *d_zdx_status = nullptr;
+    uint8_t *d_zdx_ws = nullptr;  // the workspace (ZdxLayout)
+    uint64_t cap_zdx_refs = 0, cap_zdx_lens = 0, cap_zdx_frm = 0, cap_zdx_place = 0,
+             cap_zdx_order = 0, cap_zdx_status = 0, cap_zdx_ws = 0;
+    uint64_t zdx_stats[8] = {0};  // the last call's counters (rcdc_zstd_decompress_stats)
     // pack files from sealed blobs (rcdc_pack_build_raw): copy units
     uint64_t *d_copy_units = nullptr;
     uint64_t cap_copy_units = 0;
@@ -1732,6 +1756,13 @@ void rcdc_ctx_destroy(rcdc_ctx *c) {
         (void)hipFree(c->d_zck_scratch);
         (void)hipFree(c->d_zck_blk0);
         (void)hipFree(c->d_zck_blks);
+        (void)hipFree(c->d_zdx_refs);
+        (void)hipFree(c->d_zdx_lens);
+        (void)hipFree(c->d_zdx_frm);
+        (void)hipFree(c->d_zdx_place);
+        (void)hipFree(c->d_zdx_order);
+        (void)hipFree(c->d_zdx_status);
+        (void)hipFree(c->d_zdx_ws);
         (void)hipFree(c->d_copy_units);
         if (c->stream) (void)hipStreamDestroy(c->stream);
     }
@@ -2843,9 +2874,220 @@ rcdc_status zstd_check(rcdc_ctx *ctx, const void *d_frames, const void *d_data,
     return null_leave(ctx, hip_stream, st);
 }
 
+// The decompressor's workspace for nblk blocks and `data` bytes of literals
+// and sequence records: the one place its regions are laid out.
+ZdxLayout zdx_layout(uint64_t nblk, uint64_t data) {
+    auto up = [](uint64_t v) { return (v + 255) & ~255ull; };
+    ZdxLayout l;
+    l.blk_off = 0;
+    l.blk_cap = nblk * sizeof(ZdxBlk);
+    l.res_off = up(l.blk_off + l.blk_cap);
+    l.res_cap = nblk * sizeof(ZdxRes);
+    l.data_off = up(l.res_off + l.res_cap);
+    l.data_cap = data;
+    l.total = up(l.data_off + l.data_cap);
+    return l;
+}
+
+// Frame decompression: the header walk (counting), the workspace laid out
+// from what it found, then per group of whole frames the header walk again
+// (writing block descriptors), the parallel entropy stage, the in-order
+// entropy pass for the flagged frames, and the copy stage.
+rcdc_status zstd_decompress(rcdc_ctx *ctx, const void *d_frames, const rcdc_zstd_dec_ref *refs,
+                            uint32_t n, uint32_t flags, void *d_out, uint64_t *out_lens,
+                            uint32_t *status, void *hip_stream) {
+    if (!valid_ctx(ctx) || (n && (!refs || !d_frames || !d_out || !out_lens || !status)))
+        return fail(RCDC_ERR_INVALID_INPUT, "null argument");
+    if (flags) return fail(RCDC_ERR_INVALID_INPUT, "rcdc_zstd_decompress: unknown flags");
+    // the data region's cap (the one rcdc_zstd_compress documents for its slots)
+    static const uint64_t ws_max = getenv("RCDC_ZDX_WS_MAX")
+                                       ? std::max<uint64_t>(strtoull(getenv("RCDC_ZDX_WS_MAX"), nullptr, 10), 1)
+                                       : 4ull << 30;
+    static const bool blockpar = !(getenv("RCDC_ZDX_BLOCKS") && atoi(getenv("RCDC_ZDX_BLOCKS")) == 0);
+    std::lock_guard<std::mutex> lk(ctx->zdx_mu);
+    memset(ctx->zdx_stats, 0, sizeof ctx->zdx_stats);
+    if (!n) return RCDC_OK;
+    DeviceGuard g(ctx->device);
+    hipStream_t st;
+    rcdc_status rs;
+    if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
+    const uint32_t grid = (uint32_t)std::max(ctx->num_cus, 1) * zdx_waves_per_cu();
+    if ((rs = ensure_dev(&ctx->d_zdx_refs, &ctx->cap_zdx_refs, 4ull * n))) return rs;
+    if ((rs = ensure_dev(&ctx->d_zdx_lens, &ctx->cap_zdx_lens, n))) return rs;
+    if ((rs = ensure_dev(&ctx->d_zdx_frm, &ctx->cap_zdx_frm, n))) return rs;
+    if ((rs = ensure_dev(&ctx->d_zdx_place, &ctx->cap_zdx_place, n))) return rs;
+    if ((rs = ensure_dev(&ctx->d_zdx_order, &ctx->cap_zdx_order, 2ull * n + 16))) return rs;
+    if ((rs = ensure_dev(&ctx->d_zdx_status, &ctx->cap_zdx_status, n))) return rs;
+    const uint8_t *frames = (const uint8_t *)d_frames;
+    HIP_TRY(hipMemcpyAsync(ctx->d_zdx_refs, refs, sizeof(rcdc_zstd_dec_ref) * n, hipMemcpyHostToDevice, st));
+    // 1. count: blocks and workspace bytes per frame
+    const ZdxLayout none = zdx_layout(0, 0);
+    HIP_TRY(launch_zdx_blocks(frames, ctx->d_zdx_refs, n, false, !blockpar, nullptr, none, nullptr,
+                              ctx->d_zdx_frm, st));
+    std::vector<ZdxFrame> hf(n);
+    HIP_TRY(hipMemcpyAsync(hf.data(), ctx->d_zdx_frm, sizeof(ZdxFrame) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(poll_stream(st));
+    // 2. groups of whole frames within the cap (a frame above it: a group of its own)
+    struct Group {
+        uint32_t a, b;
+        uint64_t nblk, data;
+    };
+    std::vector<Group> groups;
+    std::vector<ZdxPlace> place(n);
+    uint64_t peak = 0;
+    for (uint32_t i = 0; i < n;) {
+        Group G{i, i, 0, 0};
+        while (G.b < n) {
+            const ZdxFrame &F = hf[G.b];
+            const uint64_t need = F.status ? 0 : F.need;
+            if (G.b > G.a && (G.data + need > ws_max || G.nblk + F.nblk > (1ull << 31))) break;
+            place[G.b].blk0 = G.nblk;  // (every block the walk reaches has a slot,
+            place[G.b].data0 = G.data;  //  also in a frame it then refuses)
+            G.nblk += F.nblk;
+            G.data += need;
+            G.b++;
+        }
+        peak = std::max(peak, zdx_layout(G.nblk, G.data).total);
+        groups.push_back(G);
+        i = G.b;
+    }
+    if ((rs = ensure_dev(&ctx->d_zdx_ws, &ctx->cap_zdx_ws, peak))) return rs;
+    HIP_TRY(hipMemcpyAsync(ctx->d_zdx_place, place.data(), sizeof(ZdxPlace) * n, hipMemcpyHostToDevice, st));
+    uint32_t *d_list = ctx->d_zdx_order, *d_ord = ctx->d_zdx_order + n, *ctr = ctx->d_zdx_order + 2ull * n;
+    std::vector<uint32_t> list, order;
+    // RCDC_ZDX_TIME: HIP-event times of the entropy kernels and of the copy
+    // kernel into the counters (tools/zstd_prof.py); a sync per group
+    static const bool timed = getenv("RCDC_ZDX_TIME") && atoi(getenv("RCDC_ZDX_TIME"));
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (timed)
+        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+    // 3. per group: descriptors, entropy (parallel, then in order), copy.
+    // Indices inside a group count from its first frame.
+    for (const Group &G : groups) {
+        const uint32_t m = G.b - G.a;
+        const ZdxLayout lay = zdx_layout(G.nblk, G.data);
+        list.clear();
+        order.resize(m);
+        for (uint32_t j = 0; j < m; j++) {
+            order[j] = j;
+            const ZdxFrame &F = hf[G.a + j];
+            if (F.status) continue;
+            if (F.flags & kZdxInOrder) {
+                list.push_back(j);
+                ctx->zdx_stats[2] += F.ncomp;
+            } else {
+                ctx->zdx_stats[1] += F.ncomp;
+                ctx->zdx_stats[3] += F.ntreeless;
+            }
+        }
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+            return refs[G.a + x].frame_len > refs[G.a + y].frame_len;
+        });
+        const uint64_t *grefs = ctx->d_zdx_refs + 4ull * G.a;
+        ZdxFrame *gfrm = ctx->d_zdx_frm + G.a;
+        const ZdxPlace *gplace = ctx->d_zdx_place + G.a;
+        HIP_TRY(hipMemsetAsync(ctr, 0, 16, st));
+        if (!list.empty())
+            HIP_TRY(hipMemcpyAsync(d_list, list.data(), 4ull * list.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_ord, order.data(), 4ull * m, hipMemcpyHostToDevice, st));
+        HIP_TRY(launch_zdx_blocks(frames, grefs, m, true, !blockpar, gplace, lay, ctx->d_zdx_ws, gfrm, st));
+        if (timed) HIP_TRY(hipEventRecord(ev[0], st));
+        if (blockpar)
+            HIP_TRY(launch_zdx_entropy(frames, gfrm, lay, ctx->d_zdx_ws, G.nblk, grid, ctr, st));
+        HIP_TRY(launch_zdx_inorder(frames, gfrm, gplace, d_list, (uint32_t)list.size(), lay,
+                                   ctx->d_zdx_ws, grid, ctr + 1, st));
+        if (timed) HIP_TRY(hipEventRecord(ev[1], st));
+        HIP_TRY(launch_zdx_copy(frames, grefs, gfrm, gplace, d_ord, m, lay, ctx->d_zdx_ws,
+                                (uint8_t *)d_out, ctx->d_zdx_lens + G.a, ctx->d_zdx_status + G.a, grid,
+                                ctr + 2, st));
+        if (timed) HIP_TRY(hipEventRecord(ev[2], st));
+        // the next group's uploads reuse list / order: this group's are read
+        if (groups.size() > 1 || timed) HIP_TRY(poll_stream(st));
+        if (timed) {
+            float a = 0, c = 0;
+            HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+            HIP_TRY(hipEventElapsedTime(&c, ev[1], ev[2]));
+            ctx->zdx_stats[6] += (uint64_t)(a * 1e3f);
+            ctx->zdx_stats[7] += (uint64_t)(c * 1e3f);
+        }
+    }
+    if (timed)
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    HIP_TRY(hipMemcpyAsync(status, ctx->d_zdx_status, 4ull * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_lens, ctx->d_zdx_lens, 8ull * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(poll_stream(st));
+    ctx->zdx_stats[0] = n;
+    ctx->zdx_stats[4] = groups.size();
+    ctx->zdx_stats[5] = peak;
+    return null_leave(ctx, hip_stream, st);
+}
+
+// The header walk on the host: the first frame of `frame`.
+rcdc_status zstd_frame_info(const uint8_t *f, uint64_t len, uint64_t *content_size,
+                            uint64_t *out_bound, uint32_t *nblocks) {
+    if (!f || !content_size || !out_bound || !nblocks)
+        return fail(RCDC_ERR_INVALID_INPUT, "null argument");
+    if (len < 6 || f[0] != 0x28 || f[1] != 0xB5 || f[2] != 0x2F || f[3] != 0xFD)
+        return fail(RCDC_ERR_INVALID_INPUT, "not a zstd frame");
+    const uint32_t fhd = f[4];
+    if (fhd & 8u) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: reserved bit set");
+    const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1u, cksum = (fhd >> 2) & 1u,
+                   did_flag = fhd & 3u;
+    uint64_t q = 5 + (single ? 0 : 1);
+    const uint32_t did_len = did_flag == 0 ? 0 : did_flag == 1 ? 1 : did_flag == 2 ? 2 : 4;
+    const uint32_t fcs_len = fcs_flag == 0 ? (single ? 1 : 0) : fcs_flag == 1 ? 2 : fcs_flag == 2 ? 4 : 8;
+    if (q + did_len + fcs_len > len) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: header cut off");
+    uint32_t did = 0;
+    for (uint32_t j = 0; j < did_len; j++) did |= (uint32_t)f[q + j] << (8 * j);
+    if (did) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: dictionaries are not supported");
+    q += did_len;
+    uint64_t fcs = 0;
+    for (uint32_t j = 0; j < fcs_len; j++) fcs |= (uint64_t)f[q + j] << (8 * j);
+    if (fcs_len == 2) fcs += 256;
+    q += fcs_len;
+    uint64_t bound = 0;
+    uint32_t nb = 0;
+    for (;;) {
+        if (q + 3 > len) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: block header past the end");
+        const uint32_t bh = f[q] | (f[q + 1] << 8) | ((uint32_t)f[q + 2] << 16);
+        q += 3;
+        const uint32_t last = bh & 1u, btype = (bh >> 1) & 3u, bsize = bh >> 3;
+        const uint64_t csz = btype == 1 ? 1u : bsize;
+        if (btype == 3) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: reserved block type");
+        if (q + csz > len) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: block past the end");
+        bound += btype == 2 ? (bsize ? kZstdBlock : 0u) : bsize;
+        q += csz;
+        nb++;
+        if (last) break;
+    }
+    if (cksum && q + 4 > len) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: checksum cut off");
+    *content_size = fcs_len ? fcs : UINT64_MAX;
+    *out_bound = bound;
+    *nblocks = nb;
+    return RCDC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+rcdc_status rcdc_zstd_decompress(rcdc_ctx *ctx, const void *d_frames, const rcdc_zstd_dec_ref *refs,
+                                 uint32_t n, uint32_t flags, void *d_out, uint64_t *out_lens,
+                                 uint32_t *status, void *hip_stream) {
+    return zstd_decompress(ctx, d_frames, refs, n, flags, d_out, out_lens, status, hip_stream);
+}
+
+rcdc_status rcdc_zstd_frame_info(const uint8_t *frame, uint64_t len, uint64_t *content_size,
+                                 uint64_t *out_bound, uint32_t *nblocks) {
+    return zstd_frame_info(frame, len, content_size, out_bound, nblocks);
+}
+
+rcdc_status rcdc_zstd_decompress_stats(rcdc_ctx *ctx, uint64_t out[8]) {
+    if (!valid_ctx(ctx) || !out) return fail(RCDC_ERR_INVALID_INPUT, "null argument");
+    std::lock_guard<std::mutex> lk(ctx->zdx_mu);
+    memcpy(out, ctx->zdx_stats, sizeof ctx->zdx_stats);
+    return RCDC_OK;
+}
 
 rcdc_status rcdc_zstd_check(rcdc_ctx *ctx, const void *d_frames, const void *d_data,
                             const rcdc_zstd_check_ref *refs, uint32_t n, uint32_t flags,

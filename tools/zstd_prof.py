@@ -2,7 +2,16 @@
 chunk-sized blobs (0.5-8 MiB) of random bytes, zeros, C3-style mixed runs,
 word text, CSV-like rows and code-like lines; GiB/s by HIP events, ratio, and a decode check
 of a sample (and libzstd level 3's ratio on a 16 MiB piece of each kind).
+--check: every frame decoded and compared on the device (rcdc_zstd_check),
+one line per repetition.  --decompress: every frame decompressed on the
+device (rcdc_zstd_decompress) -- the rate from HIP events, whether the output
+equals the input, the pass counters, the entropy and copy kernels' own times
+(RCDC_ZDX_TIME, a run of its own) -- and libzstd on 16 threads over the same
+frames; --dec-source libzstd decompresses libzstd's level-3 frames of the same
+blobs instead of this library's (Huffman literals, FSE tables, treeless
+blocks).
 Run under rocprofv3 --kernel-trace --stats for the per-kernel split."""
+import os
 import argparse
 import sys
 import time
@@ -22,6 +31,11 @@ ap.add_argument("--kinds", default="random,zeros,mixed,text,csv,code")
 ap.add_argument("--levels", default="0", help="comma-separated zstd levels")
 ap.add_argument("--check", action="store_true", help="also decode every frame on the device "
                 "(rcdc_zstd_check) and time it")
+ap.add_argument("--decompress", action="store_true", help="also decompress every frame on the "
+                "device (rcdc_zstd_decompress), and with libzstd on 16 threads")
+ap.add_argument("--dec-source", default="device", choices=["device", "libzstd"],
+                help="whose frames --decompress reads")
+ap.add_argument("--threads", type=int, default=16, help="libzstd threads of --decompress")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 n = int(args.gib * (1 << 30))
@@ -69,6 +83,67 @@ def fill(kind):
             o += z
 
 
+def decompress_leg(kind, ln):
+    """rcdc_zstd_decompress over this kind's frames against libzstd on
+    args.threads threads; returns the text for the kind's line."""
+    import ctypes
+    from concurrent.futures import ThreadPoolExecutor
+    from rustic_core_amd.compress import decompress_frames, decompress_stats
+    st = torch.cuda.current_stream().cuda_stream
+    nb = len(lens)
+    src, s_offs, s_lens = frames, f_offs, np.asarray(ln, np.uint64)
+    host = None
+    if args.dec_source == "libzstd":  # libzstd's level-3 frames of the same blobs
+        host_in = arena.cpu().numpy()
+        cap = [int(zr.lib().ZSTD_compressBound(x)) for x in lens]
+        h_offs = np.concatenate([[0], np.cumsum(cap[:-1])]).astype(np.uint64)
+        host = np.zeros(int(sum(cap)) + 64, np.uint8)
+
+        def comp(i):
+            return zr.compress_into(host.ctypes.data + int(h_offs[i]), cap[i],
+                                    host_in.ctypes.data + int(offs[i]), lens[i], 3)
+        with ThreadPoolExecutor(args.threads) as ex:
+            s_lens = np.array(list(ex.map(comp, range(nb))), np.uint64)
+        src, s_offs = torch.from_numpy(host).to(dev), h_offs
+        del host_in
+    out = torch.empty(n + 64, dtype=torch.uint8, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    rates = []
+    for rep in range(args.reps + 1):  # the first is the warm-up
+        e0.record()
+        ds, dl = decompress_frames(ctx, src.data_ptr(), s_offs, s_lens, out.data_ptr(), offs, lens, st)
+        e1.record()
+        torch.cuda.synchronize()
+        rates.append(n / (e0.elapsed_time(e1) / 1e3) / 2**30)
+    stats = decompress_stats(ctx)
+    equal = bool((ds == 0).all()) and bool((dl == np.asarray(lens, np.uint64)).all()) and \
+        bool(torch.equal(out[:n], arena[:n]))
+    del out
+    # libzstd on the same frames, a scratch output per thread
+    if host is None:
+        host = src.cpu().numpy()
+    L = zr.lib()
+    big = max(lens)
+
+    def dec(ids):
+        buf = ctypes.create_string_buffer(big)
+        for i in ids:
+            L.ZSTD_decompress(buf, big, host.ctypes.data + int(s_offs[i]), int(s_lens[i]))
+    t1 = time.perf_counter()
+    with ThreadPoolExecutor(args.threads) as ex:
+        list(ex.map(dec, [range(k, nb, args.threads) for k in range(args.threads)]))
+    cpu = n / (time.perf_counter() - t1) / 2**30
+    times = ""
+    if stats.get("entropy_us") or stats.get("copy_us"):
+        times = f", entropy {stats['entropy_us'] / 1e3:.1f} ms copy {stats['copy_us'] / 1e3:.1f} ms"
+    return (f", device decompress ({args.dec_source} frames, ratio {int(s_lens.sum()) / n:.3f}) "
+            f"{' '.join('%.1f' % r for r in rates[1:])} GiB/s, output equals input {equal}, "
+            f"blocks parallel {stats['blocks_parallel']} in order {stats['blocks_in_order']} "
+            f"treeless {stats['treeless_resolved']} groups {stats['groups']} "
+            f"workspace {stats['workspace_bytes'] / 2**30:.2f} GiB{times}, "
+            f"libzstd x{args.threads} {cpu:.1f} GiB/s")
+
+
 for kind in args.kinds.split(","):
   fill(kind)
   for level in [int(x) for x in args.levels.split(",")]:
@@ -93,11 +168,16 @@ for kind in args.kinds.split(","):
     chk = ""
     if args.check:
         from rustic_core_amd.compress import check_frames
-        t1 = time.perf_counter()
-        cs = check_frames(ctx, frames.data_ptr(), f_offs, ln, arena.data_ptr(), offs, lens, st)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t1
-        chk = f", device check {n / dt / 2**30:.1f} GiB/s ({int((cs != 0).sum())} bad)"
+        rates = []
+        for rep in range(args.reps + 1):  # the first is the warm-up
+            t1 = time.perf_counter()
+            cs = check_frames(ctx, frames.data_ptr(), f_offs, ln, arena.data_ptr(), offs, lens, st)
+            torch.cuda.synchronize()
+            rates.append(n / (time.perf_counter() - t1) / 2**30)
+        chk = (f", device check {' '.join('%.1f' % r for r in rates[1:])} GiB/s "
+               f"({int((cs != 0).sum())} bad)")
+    if args.decompress:
+        chk += decompress_leg(kind, ln)
     piece = arena[:16 << 20].cpu().numpy().tobytes()
     ref = sum(len(zr.compress(piece[o:o + (1 << 20)], 3)) for o in range(0, len(piece), 1 << 20))
     print(f"{kind:7s} level {level:3d} {len(lens)} blobs {n / 2**30:.1f} GiB: {ms:.2f} ms "
