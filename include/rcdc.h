@@ -418,6 +418,53 @@ rcdc_status rcdc_copy_ranges(rcdc_ctx *ctx, const void *const *d_ins, uint32_t n
                              const rcdc_copy_ref *refs, uint32_t n, void *d_out,
                              void *hip_stream);
 
+/* ---- restore: decoded blobs to their file positions (commands/restore.rs
+ * restore_contents, :630-668) -- what follows rcdc_aead_open /
+ * rcdc_zstd_decompress there.  Blob i, bytes [in_off, in_off + len) of
+ * d_ins[src], is copied to each of its destinations dests[dest0 .. dest0 +
+ * ndests): bytes [out_off, out_off + len) of d_outs[dst].  Any alignment on
+ * either side; a long blob is split over many workgroups (tiles of 64 KiB).
+ * The blob, dest, pointer and length arrays and `zero` are HOST arrays;
+ * d_ins[] / d_outs[] hold device pointers, in_lens[] / out_lens[] the sizes
+ * of those buffers.
+ *
+ * zero (nblobs bytes, may be NULL): zero[i] = 1 when every byte of blob i is
+ * 0 (SparseRestore::ByContent's `data.iter().all(|&b| b == 0)`; an empty
+ * blob gives 1), else 0.  With RCDC_PLACE_SKIP_ZERO an all-zero blob is not
+ * written (`if !is_sparse { write_at }`): its destination bytes keep what
+ * they held.  With flags 0 and zero NULL the test is left out.
+ *
+ * InvalidInput, checked before anything is launched or written: src >=
+ * n_ins, dst >= n_outs, dest0 + ndests > ndests_total, in_off + len >
+ * in_lens[src], out_off + len > out_lens[dst], unknown flag bits, a null
+ * array with a non-zero count, a null context.  Nothing outside a destination
+ * range is stored; loads touch only the 16-byte-aligned granules that hold
+ * source bytes.  Destination ranges that overlap each other or a source range
+ * are the caller's error and are not checked (a buffer may be both a source
+ * and a destination as long as the ranges are disjoint).
+ *
+ * Ordered on hip_stream; returns once the work has run and `zero` is filled.
+ * Calls on one context take turns.  nblobs == 0 launches nothing.          */
+typedef struct {
+    uint64_t in_off;   /* the blob: bytes [in_off, in_off + len) of d_ins[src]      */
+    uint64_t len;
+    uint32_t src;      /* < n_ins                                                   */
+    uint32_t dest0;    /* its destinations: dests[dest0 .. dest0 + ndests)          */
+    uint32_t ndests;   /* 0 is allowed: only the zero test                          */
+    uint32_t pad;
+} rcdc_place_blob;     /* 32 B */
+typedef struct {
+    uint64_t out_off;  /* the blob goes to [out_off, out_off + len) of d_outs[dst]  */
+    uint32_t dst;      /* < n_outs                                                  */
+    uint32_t pad;
+} rcdc_place_dest;     /* 16 B */
+#define RCDC_PLACE_SKIP_ZERO 1u
+rcdc_status rcdc_place_blobs(rcdc_ctx *ctx, const void *const *d_ins, const uint64_t *in_lens,
+                             uint32_t n_ins, const rcdc_place_blob *blobs, uint32_t nblobs,
+                             const rcdc_place_dest *dests, uint32_t ndests_total,
+                             void *const *d_outs, const uint64_t *out_lens, uint32_t n_outs,
+                             uint32_t flags, uint8_t *zero, void *hip_stream);
+
 /* ---- blob compression: backend/decrypt.rs:478-506 (`encode_all(data,
  * level)` before `Key::encrypt_data` when the repository is version 2,
  * configfile.rs:177-186), applied by the packer's process_data

@@ -12,8 +12,10 @@ from .chunker import (  # noqa: F401
     check_rabin_params, fixed_cuts, DEFAULT_CHUNK_SIZE, DEFAULT_CHUNK_MIN_SIZE,
     DEFAULT_CHUNK_MAX_SIZE,
 )
+from .restore import RestorePlan, index_lookup, restore_contents  # noqa: F401
 
 __all__ = [
     "ErrorKind", "RusticError", "Chunker", "ChunkIter", "ConfigFile", "Context",
     "RabinChunkIter", "FixedSizeChunkIter", "check_rabin_params", "fixed_cuts",
+    "RestorePlan", "index_lookup", "restore_contents",
 ]

@@ -40,6 +40,7 @@ EXPORTS = (
     "rcdc_ingest_footprint", "rcdc_ingest_mem_live", "rcdc_index_create", "rcdc_index_destroy",
     "rcdc_index_add", "rcdc_index_size", "rcdc_ingest_set_index",
     "rcdc_zstd_decompress", "rcdc_zstd_frame_info", "rcdc_zstd_decompress_stats",
+    "rcdc_place_blobs",
 )
 ABI_VERSION = 5
 
@@ -174,6 +175,8 @@ def lib() -> ctypes.CDLL:
     L.rcdc_pack_build_raw_multi.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, vp, u64, vp, vp]
     L.rcdc_copy_ranges.restype = st
     L.rcdc_copy_ranges.argtypes = [vp, vp, u32, vp, u32, vp, vp]
+    L.rcdc_place_blobs.restype = st
+    L.rcdc_place_blobs.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, u32, u32, vp, vp]
     L.rcdc_sha256_host.restype = st
     L.rcdc_sha256_host.argtypes = [vp, vp, u32, vp]
     L.rcdc_host_alloc.restype = st

@@ -28,6 +28,7 @@
 
 #include "../../include/rcdc.h"
 #include "rcdc_internal.h"
+#include "rcdc_place.h"
 
 namespace rcdc {
 int scan_threads(int code);
@@ -383,6 +384,18 @@ struct rcdc_ctx {
     // pack files from sealed blobs (rcdc_pack_build_raw): copy units
     uint64_t *d_copy_units = nullptr;
     uint64_t cap_copy_units = 0;
+    // blobs placed into files (rcdc_place_blobs): calls on one context take turns
+    std::mutex place_mu;
+    PlaceTile *d_place_tiles = nullptr;
+    uint64_t *d_place_dests = nullptr;
+    uint32_t *d_place_nz = nullptr;
+    uint64_t cap_place_tiles = 0, cap_place_dests = 0, cap_place_nz = 0;
+    uint8_t *h_place = nullptr;  // page-locked: destination addresses, read-back, tiles
+    uint64_t cap_h_place = 0;
+    // tile windows are uploaded on a stream of their own, so that window
+    // k + 1 arrives while window k runs; one event per window of a round
+    hipStream_t place_up = nullptr;
+    hipEvent_t place_ev[16] = {};
 };
 
 struct rcdc_stream {
@@ -1764,6 +1777,13 @@ void rcdc_ctx_destroy(rcdc_ctx *c) {
         (void)hipFree(c->d_zdx_status);
         (void)hipFree(c->d_zdx_ws);
         (void)hipFree(c->d_copy_units);
+        (void)hipFree(c->d_place_tiles);
+        (void)hipFree(c->d_place_dests);
+        (void)hipFree(c->d_place_nz);
+        (void)hipHostFree(c->h_place);
+        for (hipEvent_t e : c->place_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (c->place_up) (void)hipStreamDestroy(c->place_up);
         if (c->stream) (void)hipStreamDestroy(c->stream);
     }
     delete c;
@@ -3150,6 +3170,194 @@ rcdc_status rcdc_copy_ranges(rcdc_ctx *ctx, const void *const *d_ins, uint32_t n
     rcdc_status rs;
     if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
     if ((rs = copy_units_run(ctx, copies, d_out, st))) return rs;
+    return null_leave(ctx, hip_stream, st);
+}
+
+static_assert(sizeof(rcdc_place_blob) == 32, "rcdc_place_blob is 32 B");
+static_assert(sizeof(rcdc_place_dest) == 16, "rcdc_place_dest is 16 B");
+
+// Tiles a call keeps at once, in page-locked memory and on the device (32 MiB
+// of descriptors, 64 GiB of source).  A call with more runs in rounds: the
+// stream is drained and the buffers are filled again.  RCDC_PLACE_TILES:
+// another cap (the tests' rounds).
+static uint64_t place_tile_cap() {
+    uint64_t cap = 1u << 20;
+    if (const char *e = getenv("RCDC_PLACE_TILES")) cap = (uint64_t)atoll(e);
+    return std::min<uint64_t>(std::max<uint64_t>(cap, 1), 1u << 20);
+}
+
+// Decoded blobs to their file positions (restore.rs:630-668).  Everything is
+// validated before the first launch; then the tile list (rcdc_place.h) is
+// built blob by blob in page-locked memory and launched in windows that grow
+// from 4096 tiles, doubling: the first launch goes out early, later ones are
+// few, and the host builds window k + 1 while window k runs.
+rcdc_status rcdc_place_blobs(rcdc_ctx *ctx, const void *const *d_ins, const uint64_t *in_lens,
+                             uint32_t n_ins, const rcdc_place_blob *blobs, uint32_t nblobs,
+                             const rcdc_place_dest *dests, uint32_t ndests_total,
+                             void *const *d_outs, const uint64_t *out_lens, uint32_t n_outs,
+                             uint32_t flags, uint8_t *zero, void *hip_stream) {
+    if (!valid_ctx(ctx)) return fail(RCDC_ERR_INVALID_INPUT, "ctx is NULL");
+    if (flags & ~RCDC_PLACE_SKIP_ZERO)
+        return fail(RCDC_ERR_INVALID_INPUT, "flags: unknown bits 0x%x", flags & ~RCDC_PLACE_SKIP_ZERO);
+    if (nblobs && !blobs) return fail(RCDC_ERR_INVALID_INPUT, "blobs is NULL with nblobs %u", nblobs);
+    if (ndests_total && !dests)
+        return fail(RCDC_ERR_INVALID_INPUT, "dests is NULL with ndests_total %u", ndests_total);
+    if (n_ins && (!d_ins || !in_lens))
+        return fail(RCDC_ERR_INVALID_INPUT, "%s is NULL with n_ins %u", d_ins ? "in_lens" : "d_ins",
+                    n_ins);
+    if (n_outs && (!d_outs || !out_lens))
+        return fail(RCDC_ERR_INVALID_INPUT, "%s is NULL with n_outs %u",
+                    d_outs ? "out_lens" : "d_outs", n_outs);
+    if (!nblobs) return RCDC_OK;
+
+    std::lock_guard<std::mutex> lk(ctx->place_mu);
+    DeviceGuard g(ctx->device);
+    // page-locked: every destination's device address, the non-zero words
+    // read back, the tiles
+    uint64_t ntiles = 0;
+    for (uint32_t i = 0; i < nblobs; i++) ntiles += (blobs[i].len >> 16) + 1;  // an upper bound
+    const uint64_t R = std::min<uint64_t>(ntiles, place_tile_cap());
+    const uint64_t o_nz = ((uint64_t)ndests_total * 8 + 15) / 16 * 16;
+    const uint64_t o_tiles = (o_nz + (uint64_t)nblobs * 4 + 31) / 32 * 32;
+    const uint64_t need = o_tiles + R * sizeof(PlaceTile);
+    if (need > ctx->cap_h_place) {
+        if (ctx->h_place) HIP_TRY(hipHostFree(ctx->h_place));
+        ctx->h_place = nullptr;
+        ctx->cap_h_place = 0;
+        const uint64_t c = need + need / 4 + 4096;
+        HIP_TRY(hipHostMalloc((void **)&ctx->h_place, c, hipHostMallocDefault));
+        ctx->cap_h_place = c;
+    }
+    uint64_t *daddr = reinterpret_cast<uint64_t *>(ctx->h_place);
+    uint32_t *h_nz = reinterpret_cast<uint32_t *>(ctx->h_place + o_nz);
+    PlaceTile *tiles = reinterpret_cast<PlaceTile *>(ctx->h_place + o_tiles);
+    for (uint32_t i = 0; i < nblobs; i++) {
+        const rcdc_place_blob &b = blobs[i];
+        if (b.src >= n_ins)
+            return fail(RCDC_ERR_INVALID_INPUT, "blob %u: src %u >= n_ins %u", i, b.src, n_ins);
+        if (b.len > in_lens[b.src] || b.in_off > in_lens[b.src] - b.len)
+            return fail(RCDC_ERR_INVALID_INPUT,
+                        "blob %u: in_off %llu + len %llu > in_lens[%u] = %llu", i,
+                        (unsigned long long)b.in_off, (unsigned long long)b.len, b.src,
+                        (unsigned long long)in_lens[b.src]);
+        if (b.len && !d_ins[b.src])
+            return fail(RCDC_ERR_INVALID_INPUT, "blob %u: d_ins[%u] is NULL", i, b.src);
+        if ((uint64_t)b.dest0 + b.ndests > ndests_total)
+            return fail(RCDC_ERR_INVALID_INPUT, "blob %u: dest0 %u + ndests %u > ndests_total %u", i,
+                        b.dest0, b.ndests, ndests_total);
+        for (uint32_t d = b.dest0; d < b.dest0 + b.ndests; d++) {
+            const rcdc_place_dest &o = dests[d];
+            if (o.dst >= n_outs)
+                return fail(RCDC_ERR_INVALID_INPUT, "blob %u, dest %u: dst %u >= n_outs %u", i, d,
+                            o.dst, n_outs);
+            if (b.len > out_lens[o.dst] || o.out_off > out_lens[o.dst] - b.len)
+                return fail(RCDC_ERR_INVALID_INPUT,
+                            "blob %u, dest %u: out_off %llu + len %llu > out_lens[%u] = %llu", i, d,
+                            (unsigned long long)o.out_off, (unsigned long long)b.len, o.dst,
+                            (unsigned long long)out_lens[o.dst]);
+            if (b.len && !d_outs[o.dst])
+                return fail(RCDC_ERR_INVALID_INPUT, "blob %u, dest %u: d_outs[%u] is NULL", i, d,
+                            o.dst);
+            daddr[d] = (uint64_t)(uintptr_t)d_outs[o.dst] + o.out_off;
+        }
+    }
+
+    const bool skip = (flags & RCDC_PLACE_SKIP_ZERO) != 0, want_zero = skip || zero;
+    hipStream_t st;
+    rcdc_status rs;
+    if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
+    if ((rs = ensure_dev(&ctx->d_place_tiles, &ctx->cap_place_tiles, R))) return rs;
+    if ((rs = ensure_dev(&ctx->d_place_dests, &ctx->cap_place_dests,
+                         std::max<uint64_t>(ndests_total, 1))))
+        return rs;
+    if (ndests_total)
+        HIP_TRY(hipMemcpyAsync(ctx->d_place_dests, daddr, (size_t)ndests_total * 8,
+                               hipMemcpyHostToDevice, st));
+    if (want_zero) {
+        if ((rs = ensure_dev(&ctx->d_place_nz, &ctx->cap_place_nz, nblobs))) return rs;
+        HIP_TRY(hipMemsetAsync(ctx->d_place_nz, 0, (size_t)nblobs * 4, st));
+    }
+    if (!ctx->place_up) HIP_TRY(hipStreamCreateWithFlags(&ctx->place_up, hipStreamNonBlocking));
+    const uint32_t cus = (uint32_t)std::max(ctx->num_cus, 1);
+    bool whole = false;  // the device holds the tile list of the whole call,
+    uint64_t whole_n = 0;  // this many tiles
+    // one pass over all tiles: tiles [w0, pos) of the buffers are the window
+    // being built
+    auto pass = [&](bool write, bool zero_test, bool skip_zero) -> rcdc_status {
+        uint64_t pos = 0, w0 = 0, w = 4096, rounds = 0;
+        uint32_t win = 0;  // windows of this round
+        auto flush = [&]() -> rcdc_status {
+            if (pos == w0) return RCDC_OK;
+            // no window of a round overwrites another, and the round before
+            // has run: the upload need not wait for the kernels in flight
+            const bool side = win < sizeof ctx->place_ev / sizeof ctx->place_ev[0];
+            HIP_TRY(hipMemcpyAsync(ctx->d_place_tiles + w0, tiles + w0,
+                                   (pos - w0) * sizeof(PlaceTile), hipMemcpyHostToDevice,
+                                   side ? ctx->place_up : st));
+            if (side) {
+                hipEvent_t &ev = ctx->place_ev[win];
+                if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+                HIP_TRY(hipEventRecord(ev, ctx->place_up));
+                HIP_TRY(hipStreamWaitEvent(st, ev, 0));
+            }
+            win++;
+            HIP_TRY(launch_place(ctx->d_place_tiles + w0, (uint32_t)(pos - w0), ctx->d_place_dests,
+                                 ctx->d_place_nz, write, zero_test, skip_zero, cus, st));
+            w0 = pos;
+            w *= 2;
+            return RCDC_OK;
+        };
+        for (uint32_t i = 0; i < nblobs; i++) {
+            const rcdc_place_blob &b = blobs[i];
+            if (!b.len || (!zero_test && !b.ndests)) continue;
+            const uint64_t src = (uint64_t)(uintptr_t)d_ins[b.src] + b.in_off;
+            uint64_t aligned = kPlaceAligned;
+            for (uint32_t d = b.dest0; d < b.dest0 + b.ndests; d++)
+                if ((daddr[d] ^ src) & 15u) aligned = 0;
+            for (uint64_t c = 0; c < b.len; c += kPlaceTile) {
+                if (pos == R) {
+                    // the buffers are full: a new round once this one has run
+                    if (rcdc_status fs = flush()) return fs;
+                    HIP_TRY(poll_stream(st));
+                    pos = w0 = 0;
+                    win = 0;
+                    rounds++;
+                }
+                PlaceTile &t = tiles[pos++];
+                t.src = src + c;
+                t.len = (uint32_t)std::min<uint64_t>(kPlaceTile, b.len - c);
+                t.blob = i;
+                t.dest0 = b.dest0;
+                t.ndests = b.ndests;
+                t.off = c | aligned;
+                if (pos - w0 >= w)
+                    if (rcdc_status fs = flush()) return fs;
+            }
+        }
+        whole = rounds == 0 && zero_test;  // (a pass without the zero test leaves blobs out)
+        whole_n = pos;
+        return flush();
+    };
+    if (skip) {
+        // every tile of a blob has been tested before any of it is written
+        if ((rs = pass(false, true, false))) return rs;
+        if (whole) {
+            // the same list again: tiles of blobs without a destination fall out in the kernel
+            HIP_TRY(launch_place(ctx->d_place_tiles, (uint32_t)whole_n, ctx->d_place_dests,
+                                 ctx->d_place_nz, true, false, true, cus, st));
+        } else {
+            HIP_TRY(poll_stream(st));  // the first pass's uploads have left the host buffer
+            if ((rs = pass(true, false, true))) return rs;
+        }
+    } else {
+        if ((rs = pass(true, want_zero, false))) return rs;
+    }
+    if (zero)
+        HIP_TRY(hipMemcpyAsync(h_nz, ctx->d_place_nz, (size_t)nblobs * 4, hipMemcpyDeviceToHost,
+                               st));
+    HIP_TRY(poll_stream(st));
+    if (zero)
+        for (uint32_t i = 0; i < nblobs; i++) zero[i] = h_nz[i] ? 0 : 1;
     return null_leave(ctx, hip_stream, st);
 }
 

@@ -269,6 +269,59 @@ def copy_ranges(ctx, d_ins: Sequence[int], src, in_offs, lens, out_offs, d_out: 
         raise status_error(st, _lib.last_error())
 
 
+class PlaceBlob(ctypes.Structure):
+    """rcdc_place_blob (include/rcdc.h)."""
+    _fields_ = [("in_off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("src", ctypes.c_uint32),
+                ("dest0", ctypes.c_uint32), ("ndests", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class PlaceDest(ctypes.Structure):
+    """rcdc_place_dest (include/rcdc.h)."""
+    _fields_ = [("out_off", ctypes.c_uint64), ("dst", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(PlaceBlob) == 32 and ctypes.sizeof(PlaceDest) == 16
+PLACE_BLOB = np.dtype([("in_off", "<u8"), ("len", "<u8"), ("src", "<u4"), ("dest0", "<u4"),
+                       ("ndests", "<u4"), ("pad", "<u4")])
+PLACE_DEST = np.dtype([("out_off", "<u8"), ("dst", "<u4"), ("pad", "<u4")])
+assert PLACE_BLOB.itemsize == 32 and PLACE_DEST.itemsize == 16
+PLACE_SKIP_ZERO = 1
+
+
+def place_blobs(ctx, d_ins: Sequence[int], in_lens: Sequence[int], blobs, dests,
+                d_outs: Sequence[int], out_lens: Sequence[int], skip_zero: bool = False,
+                stream: Optional[int] = None) -> np.ndarray:
+    """rcdc_place_blobs: blob i, bytes [in_off, +len) of d_ins[src], goes to
+    each of dests[dest0 : dest0 + ndests] (out_off of d_outs[dst]).  ``blobs``
+    is a PLACE_BLOB array or rows of (in_off, len, src, dest0, ndests),
+    ``dests`` a PLACE_DEST array or rows of (out_off, dst).  Returns the zero
+    flags (uint8, 1: every byte of the blob is 0); with ``skip_zero`` those
+    blobs are not written."""
+    def rows(x, dt, names):
+        if isinstance(x, np.ndarray) and x.dtype == dt:
+            return np.ascontiguousarray(x)
+        a = np.zeros(len(x), dt)
+        for k, r in enumerate(x):
+            for name, v in zip(names, r):
+                a[k][name] = v
+        return a
+    blobs = rows(blobs, PLACE_BLOB, ("in_off", "len", "src", "dest0", "ndests"))
+    dests = rows(dests, PLACE_DEST, ("out_off", "dst"))
+    srcs = (ctypes.c_void_p * max(len(d_ins), 1))(*[int(p) for p in d_ins])
+    outs = (ctypes.c_void_p * max(len(d_outs), 1))(*[int(p) for p in d_outs])
+    il = np.asarray(list(in_lens) or [0], np.uint64)
+    ol = np.asarray(list(out_lens) or [0], np.uint64)
+    zero = np.zeros(max(len(blobs), 1), np.uint8)
+    st = _lib.lib().rcdc_place_blobs(
+        ctx.handle, ctypes.cast(srcs, ctypes.c_void_p), il.ctypes.data, len(d_ins),
+        blobs.ctypes.data, len(blobs), dests.ctypes.data, len(dests),
+        ctypes.cast(outs, ctypes.c_void_p), ol.ctypes.data, len(d_outs),
+        PLACE_SKIP_ZERO if skip_zero else 0, zero.ctypes.data, ctypes.c_void_p(stream or 0))
+    if st:
+        raise status_error(st, _lib.last_error())
+    return zero[:len(blobs)]
+
+
 def index_entries(blobs: np.ndarray, packs: np.ndarray, offsets: np.ndarray):
     """IndexPack blobs per pack (indexfile.rs IndexBlob): [(id, type, offset,
     length, uncompressed_length or None)]."""
