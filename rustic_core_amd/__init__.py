@@ -13,9 +13,13 @@ from .chunker import (  # noqa: F401
     DEFAULT_CHUNK_MAX_SIZE,
 )
 from .restore import RestorePlan, index_lookup, restore_contents  # noqa: F401
+from .repack import (  # noqa: F401
+    BlobCopier, CopyPackBlobs, CopyStats, NewPack, plan_copy, plan_repack,
+)
 
 __all__ = [
     "ErrorKind", "RusticError", "Chunker", "ChunkIter", "ConfigFile", "Context",
     "RabinChunkIter", "FixedSizeChunkIter", "check_rabin_params", "fixed_cuts",
     "RestorePlan", "index_lookup", "restore_contents",
+    "BlobCopier", "CopyPackBlobs", "CopyStats", "NewPack", "plan_copy", "plan_repack",
 ]
