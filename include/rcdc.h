@@ -770,6 +770,84 @@ uint64_t rcdc_index_size(const rcdc_index *idx);
  * into idx.                                                                */
 rcdc_status rcdc_ingest_set_index(rcdc_ingest *ing, rcdc_index *idx);
 
+/* ---- the blob index in device memory (index/binarysorted.rs) -------------
+ * ReadIndex::has / get_id (index/binarysorted.rs:230-261) for batches of ids
+ * that are already in HBM, and the packer's dedup rule (packer.rs:304-315).
+ * The reference sorts 48-byte SortedEntry records and binary-searches them;
+ * here the entries stay in the order added and an open-addressing table
+ * finds them.  (rcdc_index above is the host dedup set of the ingest engine,
+ * a different object.)
+ *
+ * Entries are numbered in the order added: an add of n ids gets the numbers
+ * [size, size + n).  locs == NULL makes id-only entries (pack =
+ * RCDC_DINDEX_NO_PACK, the other fields 0).  pack is the caller's own pack
+ * number (SortedEntry::pack_idx); uncompressed_length 0 stands for None.
+ *
+ * One id may be added any number of times, in one call or across calls.
+ * rcdc_dindex_lookup gives, per queried id, the LOWEST-numbered entry that
+ * carries it, that entry's loc, and count = how many entries carry it; a
+ * miss gives entry = RCDC_DINDEX_MISS, count = 0 and a zeroed loc.  (The
+ * reference's binary_search leaves the choice among duplicates open; here it
+ * is fixed, and it does not depend on the order in which lanes and
+ * workgroups reach the table, nor on when the table grew.)
+ *
+ * rcdc_dindex_first_new is the packer's rule for one batch: d_new[i] = 1
+ * exactly when d_select[i] != 0 (a NULL d_select selects every i), id i is
+ * not in the index, and no j < i with d_select[j] != 0 has the same id;
+ * otherwise d_new[i] = 0.  The index is not changed: the batch's own
+ * duplicates are resolved in scratch memory that the index owns and grows
+ * (blobs are indexed only once they are packed).
+ *
+ * Table contract: slots is a power of two, at least twice the entries; the
+ * home slot of an id is the little-endian uint64 of its bytes 0..8, masked
+ * with slots - 1 (SHA-256 output needs no further mixing); collisions go to
+ * the next slot, wrapping.  A slot is one 64-bit word: the entry number in
+ * the high half, the little-endian uint32 of id bytes 8..12 in the low half.
+ * Ids crafted to collide are still answered correctly, only more slowly.
+ *
+ * Ordering: rcdc_dindex_add returns once the entries are in (it first waits
+ * for the lookups queued on this index).  lookup and first_new enqueue on
+ * hip_stream (0: the legacy default stream) and are ordered on it; their
+ * outputs are valid once that stream reaches them.  Calls on one index take
+ * turns.  n == 0 launches nothing.
+ *
+ * RCDC_ERR_INVALID_INPUT before anything is launched or touched: a null
+ * index (or context / out pointer at create), a null array with n > 0
+ * (d_select and locs may be null), unknown flag bits, size + n >= 2^32 - 1
+ * (first_new: n >= 2^32 - 1).
+ *
+ * Memory: 48 bytes per entry (32 id + 16 loc, the reference's 48) in arrays
+ * that grow by doubling, plus 12 bytes per slot (8 slot + 4 count) with
+ * 2 to 4 slots per entry: 72 to 96 bytes per entry held, up to twice that
+ * reserved right after a growth.                                           */
+typedef struct rcdc_dindex rcdc_dindex;
+#define RCDC_DINDEX_MISS    0xFFFFFFFFu   /* hit.entry on a miss               */
+#define RCDC_DINDEX_NO_PACK 0xFFFFFFFFu   /* loc.pack of an id-only entry      */
+#define RCDC_DINDEX_DEVICE_PTRS 1u        /* add: ids/locs are device pointers */
+typedef struct {
+    uint32_t pack, offset, length, uncompressed_length;
+} rcdc_dindex_loc; /* 16 B */
+typedef struct {
+    uint32_t entry, count;
+    rcdc_dindex_loc loc;
+} rcdc_dindex_hit; /* 24 B */
+
+/* reserve_entries: entries the arrays and the table are sized for up front. */
+rcdc_status rcdc_dindex_create(rcdc_ctx *ctx, uint64_t reserve_entries, rcdc_dindex **out);
+void rcdc_dindex_destroy(rcdc_dindex *dx);
+uint64_t rcdc_dindex_size(const rcdc_dindex *dx); /* entries added (0 for NULL) */
+uint64_t rcdc_dindex_keys(const rcdc_dindex *dx); /* distinct ids  (0 for NULL) */
+/* ids: n x 32 bytes; locs: n records or NULL; host pointers unless flags has
+ * RCDC_DINDEX_DEVICE_PTRS (then both are read on hip_stream).              */
+rcdc_status rcdc_dindex_add(rcdc_dindex *dx, const void *ids, const rcdc_dindex_loc *locs,
+                            uint64_t n, uint32_t flags, void *hip_stream);
+/* d_ids: n x 32 bytes, d_hits: n records (4-byte aligned), both on the device. */
+rcdc_status rcdc_dindex_lookup(rcdc_dindex *dx, const void *d_ids, uint64_t n,
+                               rcdc_dindex_hit *d_hits, void *hip_stream);
+/* d_select: n bytes or NULL; d_new: n bytes; all on the device. */
+rcdc_status rcdc_dindex_first_new(rcdc_dindex *dx, const void *d_ids, uint64_t n,
+                                  const uint8_t *d_select, uint8_t *d_new, void *hip_stream);
+
 /* Page-locked and device bytes currently held by all ingest engines of the
  * process (their own buffers, as rcdc_ingest_footprint counts them).        */
 void rcdc_ingest_mem_live(uint64_t *pinned_bytes, uint64_t *device_bytes);

@@ -13,6 +13,7 @@ from .chunker import (  # noqa: F401
     DEFAULT_CHUNK_MAX_SIZE,
 )
 from .restore import RestorePlan, index_lookup, restore_contents  # noqa: F401
+from .dindex import DeviceIndex, IndexType  # noqa: F401
 from .repack import (  # noqa: F401
     BlobCopier, CopyPackBlobs, CopyStats, NewPack, plan_copy, plan_repack,
 )
@@ -20,6 +21,6 @@ from .repack import (  # noqa: F401
 __all__ = [
     "ErrorKind", "RusticError", "Chunker", "ChunkIter", "ConfigFile", "Context",
     "RabinChunkIter", "FixedSizeChunkIter", "check_rabin_params", "fixed_cuts",
-    "RestorePlan", "index_lookup", "restore_contents",
+    "RestorePlan", "index_lookup", "restore_contents", "DeviceIndex", "IndexType",
     "BlobCopier", "CopyPackBlobs", "CopyStats", "NewPack", "plan_copy", "plan_repack",
 ]

@@ -41,6 +41,8 @@ EXPORTS = (
     "rcdc_index_add", "rcdc_index_size", "rcdc_ingest_set_index",
     "rcdc_zstd_decompress", "rcdc_zstd_frame_info", "rcdc_zstd_decompress_stats",
     "rcdc_place_blobs",
+    "rcdc_dindex_create", "rcdc_dindex_destroy", "rcdc_dindex_size", "rcdc_dindex_keys",
+    "rcdc_dindex_add", "rcdc_dindex_lookup", "rcdc_dindex_first_new",
 )
 ABI_VERSION = 5
 
@@ -64,6 +66,17 @@ class PlanInfo(ctypes.Structure):
         ("walk_seg_bytes", ctypes.c_uint32),
         ("pad", ctypes.c_uint32),
     ]
+
+
+class DindexLoc(ctypes.Structure):
+    """rcdc_dindex_loc."""
+    _fields_ = [("pack", ctypes.c_uint32), ("offset", ctypes.c_uint32),
+                ("length", ctypes.c_uint32), ("uncompressed_length", ctypes.c_uint32)]
+
+
+class DindexHit(ctypes.Structure):
+    """rcdc_dindex_hit."""
+    _fields_ = [("entry", ctypes.c_uint32), ("count", ctypes.c_uint32), ("loc", DindexLoc)]
 
 
 def build(verbose: bool = False) -> str:
@@ -249,6 +262,20 @@ def lib() -> ctypes.CDLL:
     L.rcdc_plan_window.argtypes = [vp, u32, u64, u32, vp, vp]
     L.rcdc_plan_device_digests.restype = st
     L.rcdc_plan_device_digests.argtypes = [vp, P(u64)]
+    L.rcdc_dindex_create.restype = st
+    L.rcdc_dindex_create.argtypes = [vp, u64, P(vp)]
+    L.rcdc_dindex_destroy.restype = None
+    L.rcdc_dindex_destroy.argtypes = [vp]
+    L.rcdc_dindex_size.restype = u64
+    L.rcdc_dindex_size.argtypes = [vp]
+    L.rcdc_dindex_keys.restype = u64
+    L.rcdc_dindex_keys.argtypes = [vp]
+    L.rcdc_dindex_add.restype = st
+    L.rcdc_dindex_add.argtypes = [vp, vp, vp, u64, u32, vp]
+    L.rcdc_dindex_lookup.restype = st
+    L.rcdc_dindex_lookup.argtypes = [vp, vp, u64, vp, vp]
+    L.rcdc_dindex_first_new.restype = st
+    L.rcdc_dindex_first_new.argtypes = [vp, vp, u64, vp, vp, vp]
     _lib = L
     return L
 

@@ -44,6 +44,7 @@ import numpy as np
 from .chunker import ConfigFile, Context
 from .compress import check_frames, compress_blobs, make_refs as zstd_refs, zstd_bounds
 from .crypto import Key, make_refs as aead_refs
+from .dindex import DeviceIndex
 from .device import DevicePlan, sha256_device, sha256_host, sha256_host_supported
 from .errors import ErrorKind, RusticError
 from .compress import VERIFY_MESSAGE
@@ -158,7 +159,10 @@ class DeviceIngest:
 
     ``indexed``: ids the repository already holds (the index's ``has``);
     new blob ids are added to it after each call, as the packer's index
-    would.  ``extra_verify`` defaults to the config's (true)."""
+    would.  A set of 32-byte ids, or a ``dindex.DeviceIndex`` on the same
+    device: then both dedup steps run on the device id tensors
+    (``first_new``) and the new ids go in with ``add_ids``, with the same
+    results.  ``extra_verify`` defaults to the config's (true)."""
 
     def __init__(self, config: ConfigFile, key: Key, device: int = 0,
                  indexed: Optional[set] = None, extra_verify: Optional[bool] = None,
@@ -173,6 +177,9 @@ class DeviceIngest:
                                config.chunk_max_size(), device=device)
         self.sizer = PackSizer.from_config(config, 0, current_size)
         self.indexed = indexed if indexed is not None else set()
+        if isinstance(self.indexed, DeviceIndex) and self.indexed.device != device:
+            raise RusticError(ErrorKind.InvalidInput,
+                              f"the index is on device {self.indexed.device}, the ingest on {device}")
         self._plan = None
         self._layout = None
         # two sets of (short ids, long ids, processing) streams, alternating
@@ -360,7 +367,19 @@ class DeviceIngest:
         if len(sidx):
             ids[sidx] = sout[:len(sidx)].cpu().numpy()
         known = self.indexed
-        first = first_occurrences(ids, sidx, known)
+        d_ids = None
+        if isinstance(known, DeviceIndex):
+            # the ids stay where they were computed: dedup on the device
+            with torch.cuda.device(dev):
+                d_ids = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+                d_sel = torch.zeros(n, dtype=torch.uint8, device=dev)
+                if len(sidx):
+                    d_sidx = torch.from_numpy(np.asarray(sidx, np.int64)).to(dev)
+                    d_ids[d_sidx] = sout[:len(sidx)]
+                    d_sel[d_sidx] = 1
+                first = known.first_new(d_ids, d_sel).cpu().numpy()
+        else:
+            first = first_occurrences(ids, sidx, known)
         snew = np.nonzero(first & ~is_long)[0]
         t2 = time.perf_counter()
         st_short = None
@@ -393,7 +412,15 @@ class DeviceIngest:
             ms["long_ids_ready"] = (time.perf_counter() - t0) * 1e3
             if len(lidx_q):
                 ids[lidx_q] = lout[:len(lidx_q)].cpu().numpy()
-        new = first_occurrences(ids, np.arange(n), known)
+        if d_ids is not None:
+            with torch.cuda.device(dev):
+                if len(lidx_q):
+                    d_lidx = torch.from_numpy(np.asarray(lidx_q, np.int64)).to(dev)
+                    d_ids[d_lidx] = (lout[:len(lidx_q)] if lev is not None else
+                                     torch.from_numpy(np.ascontiguousarray(got, np.uint8)).to(dev))
+                new = known.first_new(d_ids).cpu().numpy()
+        else:
+            new = first_occurrences(ids, np.arange(n), known)
         assert p.done[new].all(), "a new blob was not processed"
         nidx = np.nonzero(new)[0]
         t3 = time.perf_counter()
@@ -408,7 +435,11 @@ class DeviceIngest:
                          s_proc, dev)
         # indexed only once packed (or carried in the open pack): a failed
         # _pack must not make later calls dedup these blobs away
-        self.indexed.update(map(bytes, ids[nidx]))
+        if d_ids is not None:
+            with torch.cuda.device(dev):
+                known.add_ids(d_ids[torch.from_numpy(nidx).to(dev)])
+        else:
+            self.indexed.update(map(bytes, ids[nidx]))
         ms["pack"] = (time.perf_counter() - t3) * 1e3
         ms["total"] = (time.perf_counter() - t0) * 1e3
         p.st_long = None

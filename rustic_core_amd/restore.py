@@ -46,6 +46,16 @@ def _entry(index, blob_id: bytes) -> Tuple[bytes, IndexBlob]:
     return e
 
 
+def _entries(index, content_ids) -> List[Tuple[bytes, IndexBlob]]:
+    """_entry per content id; a DeviceIndex answers them in one device call."""
+    from .dindex import DATA, DeviceIndex
+    if not isinstance(index, DeviceIndex):
+        return [_entry(index, i) for i in content_ids]
+    content_ids = [bytes(i) for i in content_ids]
+    found = index.entries(DATA, content_ids)
+    return [_entry({i: e}, i) for i, e in zip(content_ids, found)]
+
+
 def data_length(b) -> int:
     """BlobLocation::data_length (blob.rs:146-151): the uncompressed length,
     or the sealed length less the 32 bytes of sealing."""
@@ -136,7 +146,8 @@ class RestorePlan:
         branch.  ``existing``: the file already at the destination (uint8
         device tensor, or bytes, which are uploaded); it counts only when its
         length is ``size`` (get_matching_file).  ``index``: index_lookup's
-        dict.  Whether each blob is already in place (blob_matches_reader) is
+        dict, or a ``dindex.DeviceIndex`` over the same index files (one
+        ``entries`` call per file).  Whether each blob is already in place (blob_matches_reader) is
         one sha256_device call over the ranges [file_pos, file_pos +
         data_length) of ``existing``.  Returns "Existing", "Verified" or
         "Modify"."""
@@ -146,7 +157,7 @@ class RestorePlan:
         open_file = existing if n_exist is not None and n_exist == int(size) else None
         if int(size) == 0 and open_file is not None:
             return "Existing"  # an empty file of the right size
-        entries = [_entry(index, i) for i in content_ids]
+        entries = _entries(index, content_ids)
         lens = [data_length(b) for _, b in entries]
         pos = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)]).astype(np.int64)
         matches = [False] * len(entries)
