@@ -94,7 +94,7 @@ static hipError_t launch4(const uint8_t *arena, const ScanItem *items, uint32_t 
                           uint64_t *item_masks, uint32_t blocks, hipStream_t stream) {
     const bool small = prm.mask < 0xFFFFu;
     if (prm.idx_shift == 21 && !small)
-        hipLaunchKernelGGL((rcdc_scan_kernel<R, PAIR, THREADS, HIDX ? 105 : 13, false, G>), dim3(blocks),
+        hipLaunchKernelGGL((rcdc_scan_kernel<R, PAIR, THREADS, HIDX ? kTsh53 : 13, false, G>), dim3(blocks),
                            dim3(THREADS), 0, stream, arena, items, nitems, gtab, prm, sums,
                            item_masks);
     else if (small)

@@ -50,11 +50,35 @@ struct Consts {
     uint32_t kff00;     // 0xFF00 in a VGPR
     uint32_t mask;      // avg - 1 in a VGPR
     uint32_t tsh;       // deg - 8 (generic-degree path only)
+    uint32_t sh;        // deg - 40 in a VGPR (TSH >= 200)
+    // TSH >= 200: the MOD address register.  Bytes 0, 2 and 3 stay lwm; every
+    // slide rewrites byte 1 alone, so the register is never copied.  Mutable
+    // because the slides take the constants by const reference.  It is a
+    // lane's scratch register, not a constant: one Consts belongs to one
+    // thread, and mod_addr's result is dead after the next slide.  Where the
+    // Consts sits behind a reference (the walk's W.k) it stays in a VGPR only
+    // while the compiler forwards the stores: after a change to the walker,
+    // look at the walk kernel's scratch (80 bytes, none of it accessed in the
+    // unit loop; hipcc -Rpass-analysis=kernel-resource-usage and the .s).
+    mutable uint32_t ma;
 };
 
+// The slide form (TSH, below) that the degree-53 kernels are built with.  RCDC_SLIDE_ADDR2
+// (tools/ab_lib.sh) builds the two-instruction address it replaced, for A/B
+// runs from one tree.
+#ifdef RCDC_SLIDE_ADDR2
+constexpr int kTsh53 = 105;
+#else
+constexpr int kTsh53 = 205;
+#endif
+
 // MOD table address of the top byte of h (h1 = hi32(h), a1 = hi32(h << 8)).
-// TSH >= 100: compile-time shift TSH - 100 = deg - 48 straight from h1, so the
-//   address does not wait for the v_alignbit (critical path per byte:
+// TSH >= 200: as TSH >= 100, in one instruction: v_lshrrev_b32_sdwa writes
+//   the low byte of h1 >> (deg - 40) into byte 1 of k.ma and leaves the lane's
+//   table offset in the other three (critical path per byte: v_lshrrev_sdwa,
+//   ds_read_b64, v_bitop3).  6 VALU + 2 ds_read_b64 per byte;
+// 100 <= TSH < 200: compile-time shift TSH - 100 = deg - 48 straight from h1,
+//   so the address does not wait for the v_alignbit (critical path per byte:
 //   v_lshrrev, v_bitop3, ds_read_b64, v_bitop3);
 // 0 <= TSH < 100: compile-time deg - 40 from a1 (v_lshrrev by an inline
 //   constant + one v_bitop3 (x & 0xFF00) | lwm);
@@ -64,7 +88,13 @@ struct Consts {
 template <int TSH>
 __device__ __forceinline__ uint32_t mod_addr(uint32_t h0, uint32_t h1, uint32_t a1,
                                              const Consts &k) {
-    if constexpr (TSH >= 100)
+    if constexpr (TSH >= 200) {
+        asm("v_lshrrev_b32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE "
+            "src0_sel:DWORD src1_sel:DWORD"
+            : "+v"(k.ma)
+            : "v"(k.sh), "v"(h1));
+        return k.ma;
+    } else if constexpr (TSH >= 100)
         return __builtin_amdgcn_bitop3_b32(h1 >> (TSH - 100), k.kff00, k.lwm, kAndOr);
     else if constexpr (TSH >= 0)
         return __builtin_amdgcn_bitop3_b32(a1 >> TSH, k.kff00, k.lwm, kAndOr);
@@ -147,10 +177,7 @@ __device__ __forceinline__ void record_group(Chain &c, const uint32_t (&hk)[G], 
     }
 }
 
-// 64 slides over unit `un` (bytes 64 back in `uo`), 64 / G groups of G.
-// SMALL: mask < 0xFFFF, the prefilter then runs on h & mask (exact).
-// G >= 100: groups of G - 100 that keep no fingerprints: a flagged lane
-// re-rolls its group from the saved state (P ~ 2^-12 per lane-group).
+// Rare path of the re-rolled group forms (scan_unit, 100 <= G < 1000).
 template <int TSH, int G>
 __device__ __forceinline__ void rescan_group(Chain &c, uint32_t h0, uint32_t h1, const Unit &un,
                                              const Unit &uo, const uint8_t *tab, const Consts &k,
@@ -168,11 +195,45 @@ __device__ __forceinline__ void rescan_group(Chain &c, uint32_t h0, uint32_t h1,
     }
 }
 
+// 64 slides over unit `un` (bytes 64 back in `uo`), in groups.
+// SMALL: mask < 0xFFFF, the prefilter then runs on h & mask (exact).
+// G names the group form (GG positions per group):
+//   G < 100         GG = G.  The group's fingerprints are kept; the prefilter
+//                   is the plain 16-bit minimum (the compiler forms one
+//                   v_min3_u16 per two bytes); a flagged lane tests the kept
+//                   fingerprints (record_group).  The scan kernel's form.
+//   1000 <= G       GG = G - 1000.  As above, the prefilter one v_min_u16 per
+//                   byte: it issues at v_and_b32's rate, v_min3_u16 at a third
+//                   of it (profiles/slide_variants/valu_rate2.txt).  The
+//                   walk's form.
+//   100 <= G < 200  GG = G - 100.  No fingerprints kept: a flagged lane
+//                   re-rolls its group from the saved state (P ~ 2^-12 per
+//                   lane-group).  With TSH >= 200 the re-roll is no longer
+//                   folded into the group's own slides: do not pair them.
+//   200 <= G < 1000 GG = G - 200.  Re-rolled, with an exact prefilter at any
+//                   mask width (v_and_b32 per byte, v_min3_u32 per two).
+//                   Built by tools/ubench/slide_bench only, where it lost;
+//                   it stays here because the ring driver below reaches the
+//                   group forms through scan_unit alone.
 template <int TSH, bool SMALL, int G>
 __device__ __forceinline__ void scan_unit(Chain &c, const Unit &un, const Unit &uo,
                                           const uint8_t *tab, const Consts &k, bool lv,
                                           uint32_t rb) {
-    if constexpr (G >= 100) {
+    if constexpr (G >= 200 && G < 1000) {
+        constexpr int GG = G - 200;
+#pragma unroll
+        for (int g = 0; g < 64 / GG; g++) {
+            const uint32_t h0s = c.h0, h1s = c.h1;
+            uint32_t acc = ~0u;
+#pragma unroll
+            for (int j = 0; j < GG; j++) {
+                const int b = g * GG + j;
+                slide_b<TSH>(b, c.h0, c.h1, UDW(un, b >> 2), UDW(uo, b >> 2), tab, k);
+                acc = min(acc, c.h0 & k.mask);
+            }
+            if (acc == 0 && lv) rescan_group<TSH, GG>(c, h0s, h1s, un, uo, tab, k, rb + g * GG, g);
+        }
+    } else if constexpr (G >= 100 && G < 200) {
         constexpr int GG = G - 100;
 #pragma unroll
         for (int g = 0; g < 64 / GG; g++) {
@@ -190,22 +251,27 @@ __device__ __forceinline__ void scan_unit(Chain &c, const Unit &un, const Unit &
             if (acc == 0 && lv) rescan_group<TSH, GG>(c, h0s, h1s, un, uo, tab, k, rb + g * GG, g);
         }
     } else {
+        constexpr bool M2 = G >= 1000;
+        constexpr int GG = M2 ? G - 1000 : G;
 #pragma unroll
-    for (int g = 0; g < 64 / G; g++) {
-        uint32_t hk[G];
-        uint16_t acc = 0xFFFFu;
+        for (int g = 0; g < 64 / GG; g++) {
+            uint32_t hk[GG];
+            uint16_t acc = 0xFFFFu;
+            uint32_t accw = 0xFFFFu;
 #pragma unroll
-        for (int j = 0; j < G; j++) {
-            const int b = g * G + j;
-            slide_b<TSH>(b, c.h0, c.h1, UDW(un, b >> 2), UDW(uo, b >> 2), tab, k);
-            hk[j] = c.h0;
-            const uint16_t t = SMALL ? (uint16_t)(c.h0 & k.mask) : (uint16_t)c.h0;
-            acc = __builtin_elementwise_min(acc, t);
+            for (int j = 0; j < GG; j++) {
+                const int b = g * GG + j;
+                slide_b<TSH>(b, c.h0, c.h1, UDW(un, b >> 2), UDW(uo, b >> 2), tab, k);
+                hk[j] = c.h0;
+                const uint32_t t = SMALL ? (c.h0 & k.mask) : c.h0;
+                if constexpr (M2) asm("v_min_u16 %0, %1, %0" : "+v"(accw) : "v"(t));
+                else acc = __builtin_elementwise_min(acc, (uint16_t)t);
+            }
+            if constexpr (M2) acc = (uint16_t)accw;
+            // one ballot per group; the prefilter is necessary, not sufficient:
+            // flagged lanes run the exact test
+            if (acc == 0 && lv) record_group<GG>(c, hk, k.mask, rb + g * GG);
         }
-        // one ballot per group; the prefilter is necessary, not sufficient:
-        // flagged lanes run the exact test
-        if (acc == 0 && lv) record_group<G>(c, hk, k.mask, rb + g * G);
-    }
     }
 }
 
@@ -390,6 +456,8 @@ __device__ __forceinline__ Consts make_consts(uint32_t lane, uint32_t mask, uint
     k.kff00 = in_vgpr(0xFF00u);
     k.mask = in_vgpr(mask);
     k.tsh = idx_shift + 24u;  // deg - 8
+    k.sh = in_vgpr(idx_shift - 8u);
+    k.ma = k.lwm;
     return k;
 }
 

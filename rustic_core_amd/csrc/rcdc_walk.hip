@@ -48,13 +48,24 @@ using namespace rcdc;
 namespace {
 
 // Round loop shape: a ring of 4 register units refilled a 128-byte line (two
-// units) per lane at a time, and groups of 16 positions that keep no
-// fingerprints (a flagged lane re-rolls its group, P ~ 2^-12): refilled one
-// 64-byte unit at a time the line's second half was often evicted from L2
-// before its load (PMC: 1.37 x the lane bytes fetched, now 1.02 x; walk
-// 9.83 -> 9.55 ms on C3).  Keeping the 16 fingerprints would not fit the
-// 4-unit ring in 128 VGPRs.
-constexpr int kWR = 4, kWG = 116;
+// units) per lane at a time: refilled one 64-byte unit at a time the line's
+// second half was often evicted from L2 before its load (PMC: 1.37 x the lane
+// bytes fetched, now 1.02 x; walk 9.83 -> 9.55 ms on C3).
+// Groups of 16 positions whose fingerprints are kept for the exact test of a
+// flagged lane, with one v_min_u16 per byte as the prefilter (G = 1016).  The
+// re-rolled form (116) was compiled into the same 16 kept registers while the
+// slide was free of inline assembly (the re-roll's slides were common
+// subexpressions of the group's); with the one-instruction MOD address it is a
+// true re-roll and far slower (C3 11.6 ms against 8.7; profiles/slide_variants/).
+// RCDC_SLIDE_ADDR2 builds the loop as it was before both (tools/ab_lib.sh).
+#ifndef RCDC_WALK_G  // (A/B: another group form from the same tree)
+#ifdef RCDC_SLIDE_ADDR2
+#define RCDC_WALK_G 116
+#else
+#define RCDC_WALK_G 1016
+#endif
+#endif
+constexpr int kWR = 4, kWG = RCDC_WALK_G;
 constexpr bool kWPair = true;
 constexpr uint64_t kNoCut = ~0ull;
 constexpr uint64_t kOpen = ~0ull - 1;
@@ -1786,7 +1797,7 @@ hipError_t launch_walk(const uint8_t *arena, const StreamDesc *sds, const WalkUn
 #define RCDC_WALK_LAUNCH(TSH, SM)                                                                  \
     hipLaunchKernelGGL((rcdc_walk_kernel<TSH, SM>), dim3(blocks), dim3(1024), 0, stream, arena,   \
                        sds, units, prm, gtab, piece_cuts, pstatus, ctr)
-    if (prm.idx_shift == 21 && !small) RCDC_WALK_LAUNCH(105, false);
+    if (prm.idx_shift == 21 && !small) RCDC_WALK_LAUNCH(kTsh53, false);
     else if (small) RCDC_WALK_LAUNCH(-1, true);
     else RCDC_WALK_LAUNCH(-1, false);
 #undef RCDC_WALK_LAUNCH
@@ -1812,8 +1823,8 @@ hipError_t launch_walk_chain(const uint8_t *arena, const StreamDesc *sds, const 
                        stream,                                                                     \
                        arena, sds, units, prm, gtab, piece_cuts, pstatus, bres, ctr, fixlist)
     // (the wide form only for the default degree: pipelined C3 / C4 plans)
-    if (prm.idx_shift == 21 && !small && wide) RCDC_CHK_LAUNCH(105, false, 1024);
-    else if (prm.idx_shift == 21 && !small) RCDC_CHK_LAUNCH(105, false, 512);
+    if (prm.idx_shift == 21 && !small && wide) RCDC_CHK_LAUNCH(kTsh53, false, 1024);
+    else if (prm.idx_shift == 21 && !small) RCDC_CHK_LAUNCH(kTsh53, false, 512);
     else if (small) RCDC_CHK_LAUNCH(-1, true, 512);
     else RCDC_CHK_LAUNCH(-1, false, 512);
 #undef RCDC_CHK_LAUNCH
@@ -1827,7 +1838,7 @@ hipError_t launch_walk_chain(const uint8_t *arena, const StreamDesc *sds, const 
     hipLaunchKernelGGL((rcdc_walk_fixup_kernel<TSH, SM>), dim3(fix_blocks), dim3(1024), 0, stream, \
                        arena, sds, units, prm, gtab, piece_cuts, pstatus, bres, ctr, fixlist,      \
                        fix_cuts, fixres)
-    if (prm.idx_shift == 21 && !small) RCDC_FIX_LAUNCH(105, false);
+    if (prm.idx_shift == 21 && !small) RCDC_FIX_LAUNCH(kTsh53, false);
     else if (small) RCDC_FIX_LAUNCH(-1, true);
     else RCDC_FIX_LAUNCH(-1, false);
 #undef RCDC_FIX_LAUNCH

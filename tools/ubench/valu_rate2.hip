@@ -47,6 +47,12 @@ __global__ __launch_bounds__(1024) void k(uint32_t *out, uint32_t seed) {
                 if constexpr (OP == 27) { asm volatile("v_cmp_eq_u32_e64 %2, 0, %0" : "+v"(x) : "v"(r[(i + 1) % CHAINS]), "s"(m64)); }
                 if constexpr (OP == 28) { asm volatile("v_cmp_gt_u32 vcc, 0x1000, %0" : "+v"(x) :: "vcc"); }
                 if constexpr (OP == 29) { asm volatile("v_perm_b32 %0, %0, %1, %2" : "+v"(x) : "v"(r[(i + 1) % CHAINS]), "s"(s1)); }
+                if constexpr (OP == 30) { asm volatile("v_xor_b32 %0, %1, %0" : "+v"(x) : "v"(r[(i + 1) % CHAINS])); }
+                if constexpr (OP == 31) { asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(x) : "v"(r[(i + 1) % CHAINS]), "v"(r[(i + 2) % CHAINS])); }
+                if constexpr (OP == 32) { asm volatile("v_min3_u16 %0, %0, %1, %2" : "+v"(x) : "v"(r[(i + 1) % CHAINS]), "v"(r[(i + 2) % CHAINS])); }
+                if constexpr (OP == 33) { asm volatile("v_lshrrev_b32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(x) : "v"(r[(i + 1) % CHAINS]), "v"(r[(i + 2) % CHAINS])); }
+                if constexpr (OP == 34) { asm volatile("v_min_u16 %0, %1, %0" : "+v"(x) : "v"(r[(i + 1) % CHAINS])); }
+                if constexpr (OP == 35) { asm volatile("v_pk_min_u16 %0, %0, %1" : "+v"(x) : "v"(r[(i + 1) % CHAINS])); }
                 r[i] = x;
             }
         }
@@ -104,5 +110,11 @@ int main() {
     { double t = run<27>(d, cus); printf("%-22s %.4f ns/wave-instr/CU  (%.2f x v_and vgpr)\n", "v_cmp_eq_u32 (e64 s)", t, t / base); }
     { double t = run<28>(d, cus); printf("%-22s %.4f ns/wave-instr/CU  (%.2f x v_and vgpr)\n", "v_cmp_gt_u32 vcc", t, t / base); }
     { double t = run<29>(d, cus); printf("%-22s %.4f ns/wave-instr/CU  (%.2f x v_and vgpr)\n", "v_perm sgpr sel", t, t / base); }
+    { double t = run<30>(d, cus); printf("%-22s %.4f ns/wave-instr/CU  (%.2f x v_and vgpr)\n", "v_xor_b32 vgpr", t, t / base); }
+    { double t = run<31>(d, cus); printf("%-22s %.4f ns/wave-instr/CU  (%.2f x v_and vgpr)\n", "v_bitop3 vgpr (xor3)", t, t / base); }
+    { double t = run<32>(d, cus); printf("%-22s %.4f ns/wave-instr/CU  (%.2f x v_and vgpr)\n", "v_min3_u16", t, t / base); }
+    { double t = run<33>(d, cus); printf("%-22s %.4f ns/wave-instr/CU  (%.2f x v_and vgpr)\n", "v_lshrrev sdwa->byte1", t, t / base); }
+    { double t = run<34>(d, cus); printf("%-22s %.4f ns/wave-instr/CU  (%.2f x v_and vgpr)\n", "v_min_u16", t, t / base); }
+    { double t = run<35>(d, cus); printf("%-22s %.4f ns/wave-instr/CU  (%.2f x v_and vgpr)\n", "v_pk_min_u16", t, t / base); }
     return 0;
 }
