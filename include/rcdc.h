@@ -848,6 +848,94 @@ rcdc_status rcdc_dindex_lookup(rcdc_dindex *dx, const void *d_ids, uint64_t n,
 rcdc_status rcdc_dindex_first_new(rcdc_dindex *dx, const void *d_ids, uint64_t n,
                                   const uint8_t *d_select, uint8_t *d_new, void *hip_stream);
 
+/* ---- index files parsed on the device (repofile/indexfile.rs) -------------
+ * What every command does first (stream_all::<IndexFile> into IndexCollector,
+ * index/binarysorted.rs:127-163), for index files whose decoded JSON text is
+ * already in HBM: n_files refs (off, len) into one arena d_json of json_len
+ * bytes.  The output is what IndexCollector's Extend<IndexPack> keeps, as
+ * device arrays that go straight to rcdc_dindex_add with
+ * RCDC_DINDEX_DEVICE_PTRS.
+ *
+ * The device parses a strict grammar G and nothing else.  A file outside G
+ * is no error: its status is RCDC_IXPARSE_NOT_PARSED, it adds nothing to any
+ * output, the numbering of the other files does not depend on it, and the
+ * caller parses it on the host.  G (no backslash anywhere; whitespace is
+ * space, \t, \n, \r, between any two tokens and around the root; trailing
+ * bytes other than whitespace are outside G):
+ *   root  {"supersedes": null | [id, ...], "packs": [pack, ...],
+ *          "packs_to_delete": [pack, ...]}       packs required
+ *   pack  {"id": id, "blobs": [blob, ...], "time": null | string,
+ *          "size": null | int}                   id and blobs required
+ *   blob  {"id": id, "type": "data" | "tree", "offset": int, "length": int,
+ *          "uncompressed_length": null | int != 0}   the first four required
+ *   id    a string of exactly 64 hex digits, either case
+ *   int   decimal digits, no sign / fraction / exponent / leading zero,
+ *         at most 2^32 - 1
+ *   string (time)  bytes 0x20..0x7E without '"' and '\'
+ * Keys come in any order, each at most once; any other key is outside G.
+ *
+ * Output, exactly the collector's rule: packs in file order, then in the
+ * order of "packs" ("packs_to_delete" is validated and counted only).  A
+ * pack goes to the type of its first blob (an empty pack to data, type 0),
+ * gets the next pack number of that type counted from pack_base[type], and
+ * all its blobs become entries of that type in order: d_ids[type] gets
+ * 32 bytes per entry, d_locs[type] one {pack number, offset, length,
+ * uncompressed_length or 0}.  d_ids[t] == NULL: entries of type t are
+ * counted, not written; d_locs[t] == NULL: only the ids are written.
+ * files (host, n_files records) gets the status and the counts per file,
+ * packs (host) one record per collected pack in order: id, type, number and
+ * pack_size() (size if present, else sum(length + 37 or 41) + 36,
+ * indexfile.rs:108-112).
+ *
+ * Bound (rcdc_index_parse_bound): the smallest blob object of G,
+ *   {"id":"<64>","type":"data","offset":0,"length":0}
+ * has 109 bytes and every blob but the last of an array is followed by a
+ * comma, so len bytes hold at most (len + 1) / 110 entries; the smallest
+ * pack object, {"id":"<64>","blobs":[]}, has 84 bytes, so at most
+ * (len + 1) / 85 packs.  cap_entries (the capacity of each of d_ids[t] and
+ * d_locs[t], in entries) and cap_packs must be at least the sum of the
+ * bounds over the batch's files.
+ *
+ * refs, files, packs, pack_base and result are host memory; the work is
+ * queued on hip_stream and the call returns once it has drained.
+ * RCDC_ERR_INVALID_INPUT before anything is launched: a null context, a
+ * null array with n_files > 0 (d_ids / d_locs entries may be null), a ref
+ * outside the arena, capacities below the bound, a bound of 2^32 - 1
+ * entries or more.  n_files == 0 launches nothing.
+ *
+ * RCDC_IXPARSE_TILE: the structural pass works on tiles of this many bytes,
+ * counted from the 16-byte boundary at or before each file's first byte.   */
+#define RCDC_IXPARSE_TILE       4096u
+#define RCDC_IXPARSE_OK         0u
+#define RCDC_IXPARSE_NOT_PARSED 1u
+typedef struct {
+    uint64_t off, len;
+} rcdc_ixparse_ref; /* 16 B */
+typedef struct {
+    uint32_t status;          /* RCDC_IXPARSE_OK / RCDC_IXPARSE_NOT_PARSED */
+    uint32_t packs[2];        /* collected packs per type                   */
+    uint32_t packs_to_delete; /* pack objects in "packs_to_delete"          */
+    uint32_t entries[2];      /* entries per type                           */
+} rcdc_ixparse_file; /* 24 B */
+typedef struct {
+    uint8_t id[32];
+    uint32_t type, number;
+    uint64_t size; /* IndexPack::pack_size() */
+} rcdc_ixparse_pack; /* 48 B */
+typedef struct {
+    uint64_t packs[2], entries[2];
+    uint64_t files_not_parsed;
+} rcdc_ixparse_result; /* 40 B */
+
+void rcdc_index_parse_bound(uint64_t len, uint64_t *max_entries, uint64_t *max_packs);
+uint32_t rcdc_index_parse_tile(void); /* == RCDC_IXPARSE_TILE */
+rcdc_status rcdc_index_parse(rcdc_ctx *ctx, const void *d_json, uint64_t json_len,
+                             const rcdc_ixparse_ref *refs, uint32_t n_files,
+                             const uint32_t pack_base[2], void *const d_ids[2],
+                             rcdc_dindex_loc *const d_locs[2], uint64_t cap_entries,
+                             rcdc_ixparse_file *files, rcdc_ixparse_pack *packs,
+                             uint64_t cap_packs, rcdc_ixparse_result *result, void *hip_stream);
+
 /* Page-locked and device bytes currently held by all ingest engines of the
  * process (their own buffers, as rcdc_ingest_footprint counts them).        */
 void rcdc_ingest_mem_live(uint64_t *pinned_bytes, uint64_t *device_bytes);

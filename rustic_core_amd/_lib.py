@@ -43,6 +43,7 @@ EXPORTS = (
     "rcdc_place_blobs",
     "rcdc_dindex_create", "rcdc_dindex_destroy", "rcdc_dindex_size", "rcdc_dindex_keys",
     "rcdc_dindex_add", "rcdc_dindex_lookup", "rcdc_dindex_first_new",
+    "rcdc_index_parse", "rcdc_index_parse_bound", "rcdc_index_parse_tile",
 )
 ABI_VERSION = 5
 
@@ -77,6 +78,29 @@ class DindexLoc(ctypes.Structure):
 class DindexHit(ctypes.Structure):
     """rcdc_dindex_hit."""
     _fields_ = [("entry", ctypes.c_uint32), ("count", ctypes.c_uint32), ("loc", DindexLoc)]
+
+
+class IxparseRef(ctypes.Structure):
+    """rcdc_ixparse_ref."""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64)]
+
+
+class IxparseFile(ctypes.Structure):
+    """rcdc_ixparse_file."""
+    _fields_ = [("status", ctypes.c_uint32), ("packs", ctypes.c_uint32 * 2),
+                ("packs_to_delete", ctypes.c_uint32), ("entries", ctypes.c_uint32 * 2)]
+
+
+class IxparsePack(ctypes.Structure):
+    """rcdc_ixparse_pack."""
+    _fields_ = [("id", ctypes.c_uint8 * 32), ("type", ctypes.c_uint32),
+                ("number", ctypes.c_uint32), ("size", ctypes.c_uint64)]
+
+
+class IxparseResult(ctypes.Structure):
+    """rcdc_ixparse_result."""
+    _fields_ = [("packs", ctypes.c_uint64 * 2), ("entries", ctypes.c_uint64 * 2),
+                ("files_not_parsed", ctypes.c_uint64)]
 
 
 def build(verbose: bool = False) -> str:
@@ -276,6 +300,12 @@ def lib() -> ctypes.CDLL:
     L.rcdc_dindex_lookup.argtypes = [vp, vp, u64, vp, vp]
     L.rcdc_dindex_first_new.restype = st
     L.rcdc_dindex_first_new.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.rcdc_index_parse_bound.restype = None
+    L.rcdc_index_parse_bound.argtypes = [u64, P(u64), P(u64)]
+    L.rcdc_index_parse_tile.restype = u32
+    L.rcdc_index_parse_tile.argtypes = []
+    L.rcdc_index_parse.restype = st
+    L.rcdc_index_parse.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, u64, vp, vp, u64, vp, vp]
     _lib = L
     return L
 
