@@ -936,6 +936,112 @@ rcdc_status rcdc_index_parse(rcdc_ctx *ctx, const void *d_json, uint64_t json_le
                              rcdc_ixparse_file *files, rcdc_ixparse_pack *packs,
                              uint64_t cap_packs, rcdc_ixparse_result *result, void *hip_stream);
 
+/* ---- prune's plan on the device (commands/prune.rs) -------------------------
+ * The per-blob part of PrunePlan::from_prune_options for index entries that
+ * are in HBM: count_used_blobs (prune.rs:770-784), the sequential marking of
+ * PackInfo::from_pack (:1495-1568) over all packs, its sums per pack, and the
+ * pick of the blobs a repack keeps (:1092-1095, :1320-1321).  Thresholds, the
+ * candidate sort and every decision per pack stay with the caller.
+ *
+ * rcdc_prune_create takes the m used ids (m x 32 bytes on the device) and
+ * builds an rcdc_dindex of ids without locations over them; the USED NUMBER
+ * of an id is its row.  The ids must be distinct (the reference holds them
+ * in a map): a repeated id is RCDC_ERR_INVALID_INPUT.  The ids are copied.
+ *
+ * rcdc_prune_set_entries gives the entries: entry e has its 32 id bytes at
+ * d_ids + e * id_stride, its length (uint32) at d_len + e * len_stride and
+ * its uncompressed length (uint32, 0 for none) at d_ulen + e * ulen_stride;
+ * strides are in bytes, so the d_ids / d_locs arrays of rcdc_index_parse
+ * pass as they are (id_stride 32; &d_locs->length and
+ * &d_locs->uncompressed_length with stride 16).  Lengths must be 4-byte
+ * aligned.  The arrays are read, never copied to the host, and must stay
+ * valid and unchanged while the handle uses them (until the next
+ * set_entries or destroy).  ranges[p] = {first entry, count} is pack p, p
+ * being its place in PROCESSING ORDER (prune.rs:835-842: marked packs, then
+ * unmarked ones).  Ranges may lie anywhere in the arrays and must not
+ * overlap; an entry outside every range does not exist for the plan.  The
+ * call looks every entry id up in the used table (the join) and is ordered
+ * on hip_stream.
+ *
+ * rcdc_prune_mark writes
+ *   d_counts[j], j < m: min(entries in ranges that carry used id j, 255);
+ *   d_used[e],  e < n: 1 where PackInfo::from_pack counts entry e as used,
+ *                      else 0 (0 outside every range);
+ *   packs[p] (host):   the PackInfo sums of pack p and whether every blob
+ *                      of it has an uncompressed length (1 for an empty pack);
+ *   result (host):     used ids with count 0 and the lowest such j
+ *                      (RCDC_PRUNE_NONE if none), the rounds the marking
+ *                      took, the entries of ids with two or more entries,
+ *                      and the device time of the marking and of the sums.
+ * The marking is exactly the sequential rule, on every input.  Its parallel
+ * form: an id with one entry makes its pack needed at once.  For an id with
+ * k >= 2 entries, sorted by processing position (rocPRIM radix sort over
+ * these entries only), the first min(k, 255) are live; the pack of the last
+ * live entry is needed unless an earlier pack with a live entry is; a pack
+ * is not needed once every id whose last live entry it holds was taken by
+ * an earlier needed pack.  One ROUND is one launch over the ids with k >= 2
+ * in which each walks on through its live entries as far as the packs'
+ * states are decided.  The lowest undecided pack is decided in every round,
+ * so n_packs rounds are the most; the host reads one counter (ids not yet
+ * settled) between rounds and gives RCDC_ERR_INTERNAL past n_packs + 1.
+ * No kernel waits for a value that another lane is yet to write; pack
+ * states, per-id taken words and per-pack minima are agent-scope atomics.
+ * The call returns when its outputs are written (it waits for hip_stream).
+ *
+ * rcdc_prune_keep: kinds[p] (host) is 0, RCDC_PRUNE_KEEP (the pack is Keep
+ * or Recover) or RCDC_PRUNE_REPACK; file_rank[p] (host) is the place of
+ * pack p in FILE ORDER, a permutation of 0..n_packs-1.  d_keep[e] = 1 where
+ * entry e is in a REPACK pack, its id is a used id, no KEEP pack holds that
+ * id, and e is the first entry of the id among the REPACK packs in file
+ * order; else 0.  Two passes over the entries: an atomic or of a block flag
+ * and an atomic min of the file-order position per used id, then the
+ * compare.  Ordered on hip_stream; d_keep is valid once it gets there.
+ *
+ * RCDC_ERR_INVALID_INPUT before anything is launched or written: a null
+ * handle, a null array with a non-zero count, n or m >= 2^32 - 1, a range
+ * past n, overlapping ranges, a pack of 65 536 entries or more (the
+ * reference's u16 counts), an unaligned length array or stride, a kind above
+ * 2, a file_rank that is no permutation, mark or keep before set_entries.
+ *
+ * Memory: 28 bytes per entry (24 the join's hit, 4 the pack number), 28 per
+ * entry of an id with two or more entries while mark runs, 16 per used id
+ * beside the table, 32 per pack.                                           */
+typedef struct rcdc_prune rcdc_prune;
+#define RCDC_PRUNE_NONE   0xFFFFFFFFu
+#define RCDC_PRUNE_KEEP   1u
+#define RCDC_PRUNE_REPACK 2u
+#define RCDC_PRUNE_MAX_PACK_ENTRIES 65535u
+typedef struct {
+    uint64_t first;
+    uint32_t count, pad;
+} rcdc_prune_range; /* 16 B */
+typedef struct {
+    uint64_t used_size, unused_size;
+    uint32_t used_blobs, unused_blobs;
+    uint32_t compressed, pad;
+} rcdc_prune_pack; /* 32 B */
+typedef struct {
+    uint64_t missing;        /* used ids with count 0          */
+    uint64_t first_missing;  /* lowest such row, or RCDC_PRUNE_NONE */
+    uint64_t dup_entries;    /* entries of ids with >= 2 entries */
+    uint32_t rounds, pad;
+    float mark_ms, sums_ms;  /* device time, HIP events        */
+} rcdc_prune_result; /* 40 B */
+
+rcdc_status rcdc_prune_create(rcdc_ctx *ctx, const void *d_used_ids, uint64_t m,
+                              void *hip_stream, rcdc_prune **out);
+void rcdc_prune_destroy(rcdc_prune *pr);
+rcdc_status rcdc_prune_set_entries(rcdc_prune *pr, const void *d_ids, uint64_t id_stride,
+                                   const void *d_len, uint64_t len_stride, const void *d_ulen,
+                                   uint64_t ulen_stride, uint64_t n,
+                                   const rcdc_prune_range *ranges, uint64_t n_packs,
+                                   void *hip_stream);
+rcdc_status rcdc_prune_mark(rcdc_prune *pr, uint8_t *d_counts, uint8_t *d_used,
+                            rcdc_prune_pack *packs, rcdc_prune_result *result,
+                            void *hip_stream);
+rcdc_status rcdc_prune_keep(rcdc_prune *pr, const uint8_t *kinds, const uint32_t *file_rank,
+                            uint8_t *d_keep, void *hip_stream);
+
 /* Page-locked and device bytes currently held by all ingest engines of the
  * process (their own buffers, as rcdc_ingest_footprint counts them).        */
 void rcdc_ingest_mem_live(uint64_t *pinned_bytes, uint64_t *device_bytes);

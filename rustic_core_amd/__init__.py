@@ -17,10 +17,14 @@ from .dindex import DeviceIndex, IndexType  # noqa: F401
 from .repack import (  # noqa: F401
     BlobCopier, CopyPackBlobs, CopyStats, NewPack, plan_copy, plan_repack,
 )
+from .prune import (  # noqa: F401
+    LimitOption, PackStatus, PackToDo, PrunePlan, PruneOptions, PruneStats,
+)
 
 __all__ = [
     "ErrorKind", "RusticError", "Chunker", "ChunkIter", "ConfigFile", "Context",
     "RabinChunkIter", "FixedSizeChunkIter", "check_rabin_params", "fixed_cuts",
     "RestorePlan", "index_lookup", "restore_contents", "DeviceIndex", "IndexType",
     "BlobCopier", "CopyPackBlobs", "CopyStats", "NewPack", "plan_copy", "plan_repack",
+    "LimitOption", "PackStatus", "PackToDo", "PrunePlan", "PruneOptions", "PruneStats",
 ]

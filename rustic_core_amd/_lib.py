@@ -44,6 +44,8 @@ EXPORTS = (
     "rcdc_dindex_create", "rcdc_dindex_destroy", "rcdc_dindex_size", "rcdc_dindex_keys",
     "rcdc_dindex_add", "rcdc_dindex_lookup", "rcdc_dindex_first_new",
     "rcdc_index_parse", "rcdc_index_parse_bound", "rcdc_index_parse_tile",
+    "rcdc_prune_create", "rcdc_prune_destroy", "rcdc_prune_set_entries", "rcdc_prune_mark",
+    "rcdc_prune_keep",
 )
 ABI_VERSION = 5
 
@@ -101,6 +103,14 @@ class IxparseResult(ctypes.Structure):
     """rcdc_ixparse_result."""
     _fields_ = [("packs", ctypes.c_uint64 * 2), ("entries", ctypes.c_uint64 * 2),
                 ("files_not_parsed", ctypes.c_uint64)]
+
+
+class PruneResult(ctypes.Structure):
+    """rcdc_prune_result."""
+    _fields_ = [("missing", ctypes.c_uint64), ("first_missing", ctypes.c_uint64),
+                ("dup_entries", ctypes.c_uint64), ("rounds", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32), ("mark_ms", ctypes.c_float),
+                ("sums_ms", ctypes.c_float)]
 
 
 def build(verbose: bool = False) -> str:
@@ -306,6 +316,16 @@ def lib() -> ctypes.CDLL:
     L.rcdc_index_parse_tile.argtypes = []
     L.rcdc_index_parse.restype = st
     L.rcdc_index_parse.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, u64, vp, vp, u64, vp, vp]
+    L.rcdc_prune_create.restype = st
+    L.rcdc_prune_create.argtypes = [vp, vp, u64, vp, P(vp)]
+    L.rcdc_prune_destroy.restype = None
+    L.rcdc_prune_destroy.argtypes = [vp]
+    L.rcdc_prune_set_entries.restype = st
+    L.rcdc_prune_set_entries.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, u64, vp]
+    L.rcdc_prune_mark.restype = st
+    L.rcdc_prune_mark.argtypes = [vp, vp, vp, vp, P(PruneResult), vp]
+    L.rcdc_prune_keep.restype = st
+    L.rcdc_prune_keep.argtypes = [vp, vp, vp, vp, vp]
     _lib = L
     return L
 
