@@ -31,6 +31,7 @@
 #include <cstdint>
 
 #include "rcdc_internal.h"
+#include "rcdc_launch.h"
 
 using namespace rcdc;
 

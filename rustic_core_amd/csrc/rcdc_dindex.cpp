@@ -23,11 +23,7 @@
 #include <vector>
 
 #include "rcdc_dindex.h"
-
-namespace rcdc {
-int ctx_device(const rcdc_ctx *ctx);
-rcdc_status set_error(rcdc_status st, const char *msg);
-}  // namespace rcdc
+#include "rcdc_host.h"
 
 using namespace rcdc;
 
@@ -54,26 +50,6 @@ namespace {
 constexpr uint64_t kMinSlots = 1024, kMinEntries = 512, kMaxEntries = 0xFFFFFFFFull;
 constexpr size_t kMaxReaders = 16;
 
-struct Guard {
-    int prev = 0;
-    explicit Guard(int dev) {
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(dev);
-    }
-    ~Guard() { (void)hipSetDevice(prev); }
-};
-
-rcdc_status hip_fail(const char *what, hipError_t e) {
-    return set_error(RCDC_ERR_INTERNAL,
-                     (std::string(what) + " failed: " + hipGetErrorString(e)).c_str());
-}
-
-#define DX_TRY(expr)                                       \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return hip_fail(#expr, e_);  \
-    } while (0)
-
 uint64_t pow2_at_least(uint64_t x) {
     uint64_t p = 1;
     while (p < x) p <<= 1;
@@ -96,7 +72,7 @@ rcdc_status grow_entries(rcdc_dindex *dx, uint64_t want, hipStream_t st) {
     const uint64_t cap = std::max({dx->cap * 2, pow2_at_least(want), kMinEntries});
     uint8_t *ids = nullptr;
     rcdc_dindex_loc *locs = nullptr;
-    DX_TRY(hipMalloc((void **)&ids, cap * 32));
+    HIP_TRY(hipMalloc((void **)&ids, cap * 32));
     if (hipError_t e = hipMalloc((void **)&locs, cap * sizeof(rcdc_dindex_loc)); e != hipSuccess) {
         (void)hipFree(ids);
         return hip_fail("hipMalloc(locs)", e);
@@ -125,7 +101,7 @@ rcdc_status grow_entries(rcdc_dindex *dx, uint64_t want, hipStream_t st) {
 rcdc_status new_table(rcdc_dindex *dx, uint64_t nslots, hipStream_t st) {
     uint64_t *slots = nullptr;
     uint32_t *counts = nullptr;
-    DX_TRY(hipMalloc((void **)&slots, nslots * 8));
+    HIP_TRY(hipMalloc((void **)&slots, nslots * 8));
     if (hipError_t e = hipMalloc((void **)&counts, nslots * 4); e != hipSuccess) {
         (void)hipFree(slots);
         return hip_fail("hipMalloc(counts)", e);
@@ -135,14 +111,14 @@ rcdc_status new_table(rcdc_dindex *dx, uint64_t nslots, hipStream_t st) {
     dx->slots = slots;
     dx->counts = counts;
     dx->nslots = nslots;
-    DX_TRY(hipMemsetAsync(slots, 0xFF, nslots * 8, st));
-    DX_TRY(hipMemsetAsync(counts, 0, nslots * 4, st));
-    DX_TRY(hipMemsetAsync(dx->d_keys, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(slots, 0xFF, nslots * 8, st));
+    HIP_TRY(hipMemsetAsync(counts, 0, nslots * 4, st));
+    HIP_TRY(hipMemsetAsync(dx->d_keys, 0, sizeof(unsigned long long), st));
     return RCDC_OK;
 }
 
 rcdc_status wait_readers(rcdc_dindex *dx) {
-    for (auto &r : dx->readers) DX_TRY(hipEventSynchronize(r.second));
+    for (auto &r : dx->readers) HIP_TRY(hipEventSynchronize(r.second));
     return RCDC_OK;
 }
 
@@ -150,22 +126,22 @@ rcdc_status wait_readers(rcdc_dindex *dx) {
 rcdc_status note_reader(rcdc_dindex *dx, hipStream_t st) {
     for (auto &r : dx->readers)
         if (r.first == st) {
-            DX_TRY(hipEventRecord(r.second, st));
+            HIP_TRY(hipEventRecord(r.second, st));
             return RCDC_OK;
         }
     if (dx->readers.size() >= kMaxReaders) {  // reuse the oldest once its work is done
         auto r = dx->readers.front();
-        DX_TRY(hipEventSynchronize(r.second));
+        HIP_TRY(hipEventSynchronize(r.second));
         dx->readers.erase(dx->readers.begin());
         r.first = st;
-        DX_TRY(hipEventRecord(r.second, st));
+        HIP_TRY(hipEventRecord(r.second, st));
         dx->readers.push_back(r);
         return RCDC_OK;
     }
     hipEvent_t ev = nullptr;
-    DX_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     dx->readers.emplace_back(st, ev);
-    DX_TRY(hipEventRecord(ev, st));
+    HIP_TRY(hipEventRecord(ev, st));
     return RCDC_OK;
 }
 
@@ -191,7 +167,7 @@ rcdc_status rcdc_dindex_create(rcdc_ctx *ctx, uint64_t reserve_entries, rcdc_din
         return set_error(RCDC_ERR_INVALID_INPUT, "rcdc_dindex_create: more than 2^32 - 2 entries");
     rcdc_dindex *dx = new rcdc_dindex;
     dx->device = ctx_device(ctx);
-    Guard g(dx->device);
+    DeviceGuard g(dx->device);
     rcdc_status rs = RCDC_OK;
     if (hipError_t e = hipMalloc((void **)&dx->d_keys, sizeof(unsigned long long)); e != hipSuccess)
         rs = hip_fail("hipMalloc(keys)", e);
@@ -216,7 +192,7 @@ rcdc_status rcdc_dindex_create(rcdc_ctx *ctx, uint64_t reserve_entries, rcdc_din
 void rcdc_dindex_destroy(rcdc_dindex *dx) {
     if (!dx) return;
     {
-        Guard g(dx->device);
+        DeviceGuard g(dx->device);
         for (auto &r : dx->readers) (void)hipEventSynchronize(r.second);
         if (dx->scratch_used) (void)hipEventSynchronize(dx->scratch_ev);
         free_all(dx);
@@ -238,7 +214,7 @@ rcdc_status rcdc_dindex_add(rcdc_dindex *dx, const void *ids, const rcdc_dindex_
         return set_error(RCDC_ERR_INVALID_INPUT,
                          "rcdc_dindex_add: the index would pass 2^32 - 2 entries");
     if (n == 0) return RCDC_OK;
-    Guard g(dx->device);
+    DeviceGuard g(dx->device);
     hipStream_t st = (hipStream_t)hip_stream;
     rcdc_status rs;
     if ((rs = wait_readers(dx))) return rs;
@@ -246,22 +222,22 @@ rcdc_status rcdc_dindex_add(rcdc_dindex *dx, const void *ids, const rcdc_dindex_
     if ((rs = grow_entries(dx, total, st))) return rs;
     const hipMemcpyKind kind =
         (flags & RCDC_DINDEX_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    DX_TRY(hipMemcpyAsync(dx->ids + dx->size * 32, ids, n * 32, kind, st));
+    HIP_TRY(hipMemcpyAsync(dx->ids + dx->size * 32, ids, n * 32, kind, st));
     if (locs)
-        DX_TRY(hipMemcpyAsync(dx->locs + dx->size, locs, n * sizeof(rcdc_dindex_loc), kind, st));
+        HIP_TRY(hipMemcpyAsync(dx->locs + dx->size, locs, n * sizeof(rcdc_dindex_loc), kind, st));
     else
-        DX_TRY(launch_dx_fill_locs(dx->locs, dx->size, n, st));
+        HIP_TRY(launch_dx_fill_locs(dx->locs, dx->size, n, st));
     if (dx->nslots < 2 * total) {
         // every entry again, into a cleared table
         if ((rs = new_table(dx, std::max(dx->nslots * 2, pow2_at_least(2 * total)), st)))
             return rs;
-        DX_TRY(launch_dx_insert(table_of(dx), 0, total, dx->d_keys, st));
+        HIP_TRY(launch_dx_insert(table_of(dx), 0, total, dx->d_keys, st));
     } else {
-        DX_TRY(launch_dx_insert(table_of(dx), dx->size, n, dx->d_keys, st));
+        HIP_TRY(launch_dx_insert(table_of(dx), dx->size, n, dx->d_keys, st));
     }
     unsigned long long keys = 0;
-    DX_TRY(hipMemcpyAsync(&keys, dx->d_keys, sizeof keys, hipMemcpyDeviceToHost, st));
-    DX_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&keys, dx->d_keys, sizeof keys, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     dx->size = total;
     dx->keys = keys;
     return RCDC_OK;
@@ -279,9 +255,9 @@ rcdc_status rcdc_dindex_lookup(rcdc_dindex *dx, const void *d_ids, uint64_t n,
                          "rcdc_dindex_lookup: ids must be 16-byte and hits 4-byte aligned");
     if (n == 0) return RCDC_OK;
     std::lock_guard<std::mutex> lk(dx->mu);
-    Guard g(dx->device);
+    DeviceGuard g(dx->device);
     hipStream_t st = (hipStream_t)hip_stream;
-    DX_TRY(launch_dx_lookup(table_of(dx), (const uint8_t *)d_ids, n, d_hits, st));
+    HIP_TRY(launch_dx_lookup(table_of(dx), (const uint8_t *)d_ids, n, d_hits, st));
     return note_reader(dx, st);
 }
 
@@ -297,22 +273,22 @@ rcdc_status rcdc_dindex_first_new(rcdc_dindex *dx, const void *d_ids, uint64_t n
                          "rcdc_dindex_first_new: ids must be 16-byte aligned");
     if (n == 0) return RCDC_OK;
     std::lock_guard<std::mutex> lk(dx->mu);
-    Guard g(dx->device);
+    DeviceGuard g(dx->device);
     hipStream_t st = (hipStream_t)hip_stream;
     const uint64_t need = std::max(pow2_at_least(2 * n), kMinSlots);
     if (need > dx->scratch_slots) {
-        if (dx->scratch_used) DX_TRY(hipEventSynchronize(dx->scratch_ev));
+        if (dx->scratch_used) HIP_TRY(hipEventSynchronize(dx->scratch_ev));
         (void)hipFree(dx->scratch);
         dx->scratch = nullptr;
         dx->scratch_slots = 0;
-        DX_TRY(hipMalloc((void **)&dx->scratch, need * 8));
+        HIP_TRY(hipMalloc((void **)&dx->scratch, need * 8));
         dx->scratch_slots = need;
     }
-    if (dx->scratch_used) DX_TRY(hipStreamWaitEvent(st, dx->scratch_ev, 0));
-    DX_TRY(hipMemsetAsync(dx->scratch, 0xFF, need * 8, st));
-    DX_TRY(launch_dx_first_new(table_of(dx), (const uint8_t *)d_ids, n, d_select, d_new,
+    if (dx->scratch_used) HIP_TRY(hipStreamWaitEvent(st, dx->scratch_ev, 0));
+    HIP_TRY(hipMemsetAsync(dx->scratch, 0xFF, need * 8, st));
+    HIP_TRY(launch_dx_first_new(table_of(dx), (const uint8_t *)d_ids, n, d_select, d_new,
                                dx->scratch, need - 1, st));
-    DX_TRY(hipEventRecord(dx->scratch_ev, st));
+    HIP_TRY(hipEventRecord(dx->scratch_ev, st));
     dx->scratch_used = true;
     return note_reader(dx, st);
 }

@@ -1,0 +1,115 @@
+// rcdc_host.h -- what the host halves of the library share: the entry points
+// rcdc_runtime.cpp exports to the other units, the device guard, the error
+// helpers and the owning device buffer.  Host code only (rcdc_host_sha.cpp is
+// built without HIP and does not include it).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+
+#include "../../include/rcdc.h"
+
+namespace rcdc {
+
+// ---- exported by rcdc_runtime.cpp ------------------------------------------
+int ctx_device(const rcdc_ctx *ctx);
+uint64_t ctx_min_size(const rcdc_ctx *ctx);
+uint64_t ctx_max_size(const rcdc_ctx *ctx);
+// sets the calling thread's rcdc_last_error text and returns st
+rcdc_status set_error(rcdc_status st, const char *msg);
+// Rebuild `pl` (created by rcdc_plan_create, its last run waited for) for a
+// new batch layout, reusing its device buffers; uploads on `up`.
+rcdc_status plan_relayout(rcdc_plan *pl, const uint64_t *offs, const uint64_t *lens, uint32_t n,
+                          uint64_t arena_len, hipStream_t up);
+
+// ---- exported by rcdc_host_sha.cpp (SHA-256 on the CPU) --------------------
+bool host_sha_supported();
+bool host_sha_ni();
+void host_sha256_many(const uint8_t *const *ptrs, const uint64_t *lens, uint32_t n,
+                      uint8_t *digests);
+void host_sha256_one(const uint8_t *p, uint64_t len, uint8_t out[32]);
+void host_sha256_ni_many(const uint8_t *const *ptrs, const uint64_t *lens, uint32_t n,
+                         uint8_t *digests, int ways);
+
+// Makes `dev` the calling thread's current device for a scope.
+struct DeviceGuard {
+    int prev = 0;
+    explicit DeviceGuard(int dev) {
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() { (void)hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+
+inline rcdc_status hip_fail(const char *what, hipError_t e) {
+    return set_error(RCDC_ERR_INTERNAL,
+                     (std::string(what) + " failed: " + hipGetErrorString(e)).c_str());
+}
+
+#define HIP_TRY(expr)                                            \
+    do {                                                         \
+        hipError_t e_ = (expr);                                  \
+        if (e_ != hipSuccess) return rcdc::hip_fail(#expr, e_);  \
+    } while (0)
+
+inline rcdc_status invalid(const char *msg) { return set_error(RCDC_ERR_INVALID_INPUT, msg); }
+
+// A device array that only grows, owned by the object that holds it.  Freed
+// by release() or the destructor: the owner makes its device current and
+// synchronises its streams before either runs.
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+
+    operator T *() const { return p_; }
+    T *get() const { return p_; }
+    uint64_t capacity() const { return cap_; }  // elements
+
+    void release() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+
+    // At least `need` elements; the contents are lost when it grows.  Grows
+    // with 25 % headroom: a reallocation's hipFree synchronises the whole
+    // device (every lane of every thread), so slowly varying sizes (stream
+    // passes of batch + tail bytes) must not reallocate each time.
+    // exact: to `need` elements and no more (prune's per-entry arrays, sized
+    // once per repository).
+    rcdc_status ensure(uint64_t need, bool exact = false) {
+        if (need <= cap_ && p_) return RCDC_OK;
+        static const bool log = getenv("RCDC_ALLOC_LOG") != nullptr;
+        if (log && p_)
+            fprintf(stderr, "rcdc: regrow %llu -> %llu x %zu B (hipFree: device sync)\n",
+                    (unsigned long long)cap_, (unsigned long long)need, sizeof(T));
+        if (p_) HIP_TRY(hipFree(p_));
+        p_ = nullptr;
+        cap_ = 0;
+        // at least 64 KiB: small per-stream arrays (walk streams, piece cuts)
+        // otherwise regrew from 1-2 elements when a layout first had more of
+        // them, each regrow a device-wide sync inside a pipeline (r5u)
+        const uint64_t n =
+            exact ? std::max<uint64_t>(need, 1)
+                  : std::max<uint64_t>(need + need / 4, std::max<uint64_t>(65536 / sizeof(T), 1));
+        HIP_TRY(hipMalloc((void **)&p_, n * sizeof(T)));
+        cap_ = n;
+        return RCDC_OK;
+    }
+
+private:
+    T *p_ = nullptr;
+    uint64_t cap_ = 0;
+};
+
+}  // namespace rcdc

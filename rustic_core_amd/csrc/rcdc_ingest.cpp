@@ -62,24 +62,8 @@
 #include <vector>
 
 #include "../../include/rcdc.h"
-
-namespace rcdc {
-rcdc_status plan_relayout(rcdc_plan *pl, const uint64_t *offs, const uint64_t *lens, uint32_t n,
-                          uint64_t arena_len, hipStream_t up);
-int ctx_device(const rcdc_ctx *ctx);
-uint64_t ctx_min_size(const rcdc_ctx *ctx);
-uint64_t ctx_max_size(const rcdc_ctx *ctx);
-rcdc_status set_error(rcdc_status st, const char *msg);
-void host_sha256_many(const uint8_t *const *ptrs, const uint64_t *lens, uint32_t n,
-                      uint8_t *digests);
-void host_sha256_one(const uint8_t *p, uint64_t len, uint8_t out[32]);
-void host_sha256_ni_many(const uint8_t *const *ptrs, const uint64_t *lens, uint32_t n,
-                         uint8_t *digests, int ways);
-hipError_t launch_stream_copy(void *dst, const void *src, uint64_t len, uint32_t blocks,
-                              hipStream_t stream);
-bool host_sha_supported();
-bool host_sha_ni();
-}  // namespace rcdc
+#include "rcdc_host.h"
+#include "rcdc_launch.h"
 
 using namespace rcdc;
 

@@ -8,6 +8,9 @@
 //                0xFFFFFFFF = no candidate
 //   item_mask[]: one u64 per ScanItem, bit l = segment l has a candidate
 //   StreamDesc[]: resolver input per stream; cuts[] / counts[] its output
+//
+// The launch functions over these types are declared in rcdc_launch.h; what
+// only host code shares (device guard, error helpers, DevBuf) is rcdc_host.h.
 #pragma once
 #include <stdint.h>
 

@@ -11,25 +11,12 @@
 #include <string>
 #include <vector>
 
+#include "rcdc_host.h"
 #include "rcdc_ixparse.h"
-
-namespace rcdc {
-int ctx_device(const rcdc_ctx *ctx);
-rcdc_status set_error(rcdc_status st, const char *msg);
-}  // namespace rcdc
 
 using namespace rcdc;
 
 namespace {
-
-struct Guard {
-    int prev = 0;
-    explicit Guard(int dev) {
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(dev);
-    }
-    ~Guard() { (void)hipSetDevice(prev); }
-};
 
 // device allocations of one call
 struct Scratch {
@@ -46,19 +33,6 @@ struct Scratch {
         return e;
     }
 };
-
-rcdc_status hip_fail(const char *what, hipError_t e) {
-    return set_error(RCDC_ERR_INTERNAL,
-                     (std::string(what) + " failed: " + hipGetErrorString(e)).c_str());
-}
-
-#define IX_TRY(expr)                                       \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return hip_fail(#expr, e_);  \
-    } while (0)
-
-rcdc_status invalid(const char *msg) { return set_error(RCDC_ERR_INVALID_INPUT, msg); }
 
 }  // namespace
 
@@ -112,7 +86,7 @@ rcdc_status rcdc_index_parse(rcdc_ctx *ctx, const void *d_json, uint64_t json_le
     *result = rcdc_ixparse_result{};
     if (n_files == 0) return RCDC_OK;
 
-    Guard g(ctx_device(ctx));
+    DeviceGuard g(ctx_device(ctx));
     hipStream_t st = (hipStream_t)hip_stream;
     Scratch sc;
     IxArgs a = {};
@@ -122,36 +96,36 @@ rcdc_status rcdc_index_parse(rcdc_ctx *ctx, const void *d_json, uint64_t json_le
     a.n_tiles = (uint32_t)n_tiles;
     rcdc_ixparse_ref *d_refs = nullptr;
     uint32_t *d_tile_first = nullptr;
-    IX_TRY(sc.get(&d_refs, n_files));
-    IX_TRY(sc.get(&d_tile_first, n_files + 1ull));
-    IX_TRY(sc.get(&a.sums, n_tiles));
-    IX_TRY(sc.get(&a.ins, n_tiles));
-    IX_TRY(sc.get(&a.counts, n_tiles + 1));
-    IX_TRY(hipMemcpyAsync(d_refs, refs, n_files * sizeof *refs, hipMemcpyHostToDevice, st));
-    IX_TRY(hipMemcpyAsync(d_tile_first, tile_first.data(), (n_files + 1ull) * 4,
+    HIP_TRY(sc.get(&d_refs, n_files));
+    HIP_TRY(sc.get(&d_tile_first, n_files + 1ull));
+    HIP_TRY(sc.get(&a.sums, n_tiles));
+    HIP_TRY(sc.get(&a.ins, n_tiles));
+    HIP_TRY(sc.get(&a.counts, n_tiles + 1));
+    HIP_TRY(hipMemcpyAsync(d_refs, refs, n_files * sizeof *refs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_tile_first, tile_first.data(), (n_files + 1ull) * 4,
                           hipMemcpyHostToDevice, st));
     a.refs = d_refs;
     a.tile_first = d_tile_first;
-    IX_TRY(launch_ix_structure(a, st));
-    IX_TRY(hipMemcpyAsync(&a.total, a.counts + n_tiles, sizeof a.total, hipMemcpyDeviceToHost, st));
-    IX_TRY(hipStreamSynchronize(st));
+    HIP_TRY(launch_ix_structure(a, st));
+    HIP_TRY(hipMemcpyAsync(&a.total, a.counts + n_tiles, sizeof a.total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
 
-    IX_TRY(sc.get(&a.blob_open, a.total.blobs));
-    IX_TRY(sc.get(&a.pack_open, a.total.packs));
-    IX_TRY(sc.get(&a.c4, a.total.c4));
-    IX_TRY(sc.get(&a.c2, a.total.c2));
-    IX_TRY(sc.get(&a.tmp_ids, (uint64_t)a.total.blobs * 32));
-    IX_TRY(sc.get(&a.tmp_blobs, a.total.blobs));
-    IX_TRY(sc.get(&a.tmp_packs, a.total.packs));
-    IX_TRY(sc.get(&a.tmp_files, n_files));
-    IX_TRY(sc.get(&a.file_bad, n_files));
+    HIP_TRY(sc.get(&a.blob_open, a.total.blobs));
+    HIP_TRY(sc.get(&a.pack_open, a.total.packs));
+    HIP_TRY(sc.get(&a.c4, a.total.c4));
+    HIP_TRY(sc.get(&a.c2, a.total.c2));
+    HIP_TRY(sc.get(&a.tmp_ids, (uint64_t)a.total.blobs * 32));
+    HIP_TRY(sc.get(&a.tmp_blobs, a.total.blobs));
+    HIP_TRY(sc.get(&a.tmp_packs, a.total.packs));
+    HIP_TRY(sc.get(&a.tmp_files, n_files));
+    HIP_TRY(sc.get(&a.file_bad, n_files));
     uint32_t *adds = nullptr;
-    IX_TRY(sc.get(&adds, ((uint64_t)a.total.packs + 1) * 4));
+    HIP_TRY(sc.get(&adds, ((uint64_t)a.total.packs + 1) * 4));
     a.adds = adds;
-    IX_TRY(sc.get(&a.files, n_files));
-    IX_TRY(sc.get(&a.packs, cap_packs));
-    IX_TRY(sc.get(&a.result, 4));
-    IX_TRY(hipMemsetAsync(a.file_bad, 0, n_files * 4ull, st));
+    HIP_TRY(sc.get(&a.files, n_files));
+    HIP_TRY(sc.get(&a.packs, cap_packs));
+    HIP_TRY(sc.get(&a.result, 4));
+    HIP_TRY(hipMemsetAsync(a.file_bad, 0, n_files * 4ull, st));
     for (int t = 0; t < 2; t++) {
         a.ids[t] = static_cast<uint8_t *>(d_ids[t]);
         a.locs[t] = d_locs[t];
@@ -159,17 +133,17 @@ rcdc_status rcdc_index_parse(rcdc_ctx *ctx, const void *d_json, uint64_t json_le
     }
     a.cap_entries = cap_entries;
     a.cap_packs = cap_packs;
-    IX_TRY(launch_ix_parse(a, st));
+    HIP_TRY(launch_ix_parse(a, st));
     uint64_t tot[4] = {0, 0, 0, 0};
-    IX_TRY(hipMemcpyAsync(tot, a.result, sizeof tot, hipMemcpyDeviceToHost, st));
-    IX_TRY(hipMemcpyAsync(files, a.files, n_files * sizeof *files, hipMemcpyDeviceToHost, st));
-    IX_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(tot, a.result, sizeof tot, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(files, a.files, n_files * sizeof *files, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     const uint64_t n_packs = tot[0] + tot[1];
     if (n_packs > cap_packs || tot[2] > cap_entries || tot[3] > cap_entries)
         return set_error(RCDC_ERR_INTERNAL, "rcdc_index_parse: more output than the bound allows");
     if (n_packs) {
-        IX_TRY(hipMemcpyAsync(packs, a.packs, n_packs * sizeof *packs, hipMemcpyDeviceToHost, st));
-        IX_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(packs, a.packs, n_packs * sizeof *packs, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     result->packs[0] = tot[0];
     result->packs[1] = tot[1];

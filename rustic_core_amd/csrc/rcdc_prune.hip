@@ -55,11 +55,11 @@
 #include <vector>
 
 #include "../../include/rcdc.h"
+#include "rcdc_host.h"
 
-namespace rcdc {
-int ctx_device(const rcdc_ctx *ctx);
-rcdc_status set_error(rcdc_status st, const char *msg);
-}  // namespace rcdc
+using rcdc::DeviceGuard;
+using rcdc::DevBuf;
+using rcdc::invalid;
 
 namespace {
 
@@ -362,50 +362,6 @@ __global__ __launch_bounds__(256) void rcdc_pr_keep_b_kernel(PrView v,
 
 // ---- the host half -----------------------------------------------------------
 
-struct Guard {
-    int prev = 0;
-    explicit Guard(int dev) {
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(dev);
-    }
-    ~Guard() { (void)hipSetDevice(prev); }
-};
-
-rcdc_status hip_fail(const char *what, hipError_t e) {
-    return rcdc::set_error(RCDC_ERR_INTERNAL,
-                           (std::string(what) + " failed: " + hipGetErrorString(e)).c_str());
-}
-
-#define PR_TRY(expr)                                       \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return hip_fail(#expr, e_);  \
-    } while (0)
-
-rcdc_status invalid(const char *msg) { return rcdc::set_error(RCDC_ERR_INVALID_INPUT, msg); }
-
-// a device allocation that only grows
-struct DevBuf {
-    void *p = nullptr;
-    uint64_t cap = 0;
-    hipError_t need(uint64_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        (void)hipFree(p);
-        p = nullptr, cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    void release() {
-        (void)hipFree(p);
-        p = nullptr, cap = 0;
-    }
-    template <typename T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-
 uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
 constexpr uint64_t kMaxCount = 0xFFFFFFFFull;  // n, m stay below it
@@ -422,39 +378,42 @@ struct rcdc_prune {
     const uint8_t *len = nullptr, *ulen = nullptr;
     uint64_t len_stride = 0, ulen_stride = 0, n = 0, n_packs = 0;
     std::vector<rcdc_prune_range> ranges;
-    DevBuf ids, hits, pack_of, first, count, prefix;
+    // device arrays, each grown to exactly the size asked for
+    DevBuf<uint8_t> ids;
+    DevBuf<rcdc_dindex_hit> hits;
+    DevBuf<uint32_t> pack_of, count, prefix;
+    DevBuf<uint64_t> first;
     // mark
-    DevBuf cnt, taken, state, pending, trigger, scalars, keys_a, keys_b, vals_a, vals_b, progress,
-        sort_tmp, packs_out;
+    DevBuf<uint32_t> cnt, taken, state, pending, trigger, vals_a, vals_b, progress;
+    DevBuf<unsigned long long> scalars;
+    DevBuf<uint64_t> keys_a, keys_b;
+    DevBuf<uint8_t> sort_tmp;
+    DevBuf<rcdc_prune_pack> packs_out;
     // keep
-    DevBuf kinds, fprefix, blocked, minpos;
+    DevBuf<uint8_t> kinds;
+    DevBuf<uint32_t> fprefix, blocked, minpos;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+
+    // destroyed with its device current (rcdc_prune_destroy: and synchronised)
+    ~rcdc_prune() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        rcdc_dindex_destroy(dx);
+    }
 };
 
 namespace {
 
 PrView view_of(const rcdc_prune *pr) {
     PrView v;
-    v.hits = pr->hits.as<rcdc_dindex_hit>();
-    v.pack_of = pr->pack_of.as<uint32_t>();
-    v.first = pr->first.as<uint64_t>();
-    v.count = pr->count.as<uint32_t>();
-    v.prefix = pr->prefix.as<uint32_t>();
+    v.hits = pr->hits;
+    v.pack_of = pr->pack_of;
+    v.first = pr->first;
+    v.count = pr->count;
+    v.prefix = pr->prefix;
     v.n = pr->n;
     v.n_packs = pr->n_packs;
     return v;
-}
-
-void free_all(rcdc_prune *pr) {
-    for (DevBuf *b : {&pr->ids, &pr->hits, &pr->pack_of, &pr->first, &pr->count, &pr->prefix,
-                      &pr->cnt, &pr->taken, &pr->state, &pr->pending, &pr->trigger, &pr->scalars,
-                      &pr->keys_a, &pr->keys_b, &pr->vals_a, &pr->vals_b, &pr->progress,
-                      &pr->sort_tmp, &pr->packs_out, &pr->kinds, &pr->fprefix, &pr->blocked,
-                      &pr->minpos})
-        b->release();
-    for (hipEvent_t e : pr->ev)
-        if (e) (void)hipEventDestroy(e);
-    rcdc_dindex_destroy(pr->dx);
 }
 
 }  // namespace
@@ -470,16 +429,15 @@ rcdc_status rcdc_prune_create(rcdc_ctx *ctx, const void *d_used_ids, uint64_t m,
     rcdc_prune *pr = new rcdc_prune;
     pr->device = rcdc::ctx_device(ctx);
     pr->m = m;
-    Guard g(pr->device);
+    DeviceGuard g(pr->device);
     rcdc_status rs = rcdc_dindex_create(ctx, m, &pr->dx);
     if (!rs) rs = rcdc_dindex_add(pr->dx, d_used_ids, nullptr, m, RCDC_DINDEX_DEVICE_PTRS, hip_stream);
     if (!rs && rcdc_dindex_keys(pr->dx) != m)
         rs = invalid("rcdc_prune_create: the used ids are not distinct");
     for (hipEvent_t &e : pr->ev)
         if (!rs)
-            if (hipError_t he = hipEventCreate(&e); he != hipSuccess) rs = hip_fail("hipEventCreate", he);
+            if (hipError_t he = hipEventCreate(&e); he != hipSuccess) rs = rcdc::hip_fail("hipEventCreate", he);
     if (rs) {
-        free_all(pr);
         delete pr;
         return rs;
     }
@@ -489,11 +447,8 @@ rcdc_status rcdc_prune_create(rcdc_ctx *ctx, const void *d_used_ids, uint64_t m,
 
 void rcdc_prune_destroy(rcdc_prune *pr) {
     if (!pr) return;
-    {
-        Guard g(pr->device);
-        (void)hipDeviceSynchronize();
-        free_all(pr);
-    }
+    DeviceGuard g(pr->device);
+    (void)hipDeviceSynchronize();
     delete pr;
 }
 
@@ -528,7 +483,7 @@ rcdc_status rcdc_prune_set_entries(rcdc_prune *pr, const void *d_ids, uint64_t i
             return invalid("rcdc_prune_set_entries: overlapping ranges");
 
     std::lock_guard<std::mutex> lk(pr->mu);
-    Guard g(pr->device);
+    DeviceGuard g(pr->device);
     hipStream_t st = (hipStream_t)hip_stream;
     pr->have_entries = false;
     pr->ranges.assign(ranges, ranges + n_packs);
@@ -542,37 +497,37 @@ rcdc_status rcdc_prune_set_entries(rcdc_prune *pr, const void *d_ids, uint64_t i
         first[p] = ranges[p].first, count[p] = ranges[p].count, prefix[p] = at;
         at += ranges[p].count;  // <= n < 2^32 - 1: the ranges do not overlap
     }
-    PR_TRY(pr->first.need(std::max<uint64_t>(n_packs, 1) * 8));
-    PR_TRY(pr->count.need(std::max<uint64_t>(n_packs, 1) * 4));
-    PR_TRY(pr->prefix.need(std::max<uint64_t>(n_packs, 1) * 4));
-    PR_TRY(pr->hits.need(std::max<uint64_t>(n, 1) * sizeof(rcdc_dindex_hit)));
-    PR_TRY(pr->pack_of.need(std::max<uint64_t>(n, 1) * 4));
+    if (rcdc_status rs = pr->first.ensure(std::max<uint64_t>(n_packs, 1), true)) return rs;
+    if (rcdc_status rs = pr->count.ensure(std::max<uint64_t>(n_packs, 1), true)) return rs;
+    if (rcdc_status rs = pr->prefix.ensure(std::max<uint64_t>(n_packs, 1), true)) return rs;
+    if (rcdc_status rs = pr->hits.ensure(std::max<uint64_t>(n, 1), true)) return rs;
+    if (rcdc_status rs = pr->pack_of.ensure(std::max<uint64_t>(n, 1), true)) return rs;
     if (n_packs) {
-        PR_TRY(hipMemcpyAsync(pr->first.p, first.data(), n_packs * 8, hipMemcpyHostToDevice, st));
-        PR_TRY(hipMemcpyAsync(pr->count.p, count.data(), n_packs * 4, hipMemcpyHostToDevice, st));
-        PR_TRY(hipMemcpyAsync(pr->prefix.p, prefix.data(), n_packs * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pr->first, first.data(), n_packs * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pr->count, count.data(), n_packs * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pr->prefix, prefix.data(), n_packs * 4, hipMemcpyHostToDevice, st));
     }
     if (n) {
         const uint8_t *ids = (const uint8_t *)d_ids;
         if (id_stride != 32 || ((uintptr_t)d_ids & 15u)) {
-            PR_TRY(pr->ids.need(n * 32));
+            if (rcdc_status rs = pr->ids.ensure(n * 32, true)) return rs;
             hipLaunchKernelGGL(rcdc_pr_gather_ids_kernel, dim3(blocks_for(n * 8)), dim3(kBlock), 0,
-                               st, ids, id_stride, n, pr->ids.as<uint8_t>());
-            PR_TRY(hipGetLastError());
-            ids = pr->ids.as<uint8_t>();
+                               st, ids, id_stride, n, pr->ids);
+            HIP_TRY(hipGetLastError());
+            ids = pr->ids;
         }
-        PR_TRY(hipMemsetAsync(pr->pack_of.p, 0xFF, n * 4, st));
+        HIP_TRY(hipMemsetAsync(pr->pack_of, 0xFF, n * 4, st));
         if (n_packs) {
             hipLaunchKernelGGL(rcdc_pr_pack_of_kernel, dim3((uint32_t)n_packs), dim3(kBlock), 0, st,
-                               pr->first.as<uint64_t>(), pr->count.as<uint32_t>(), n,
-                               pr->pack_of.as<uint32_t>());
-            PR_TRY(hipGetLastError());
+                               pr->first, pr->count, n,
+                               pr->pack_of);
+            HIP_TRY(hipGetLastError());
         }
-        if (rcdc_status rs = rcdc_dindex_lookup(pr->dx, ids, n, pr->hits.as<rcdc_dindex_hit>(), st))
+        if (rcdc_status rs = rcdc_dindex_lookup(pr->dx, ids, n, pr->hits, st))
             return rs;
     }
     // the host vectors above must outlive their copies
-    PR_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     pr->have_entries = true;
     return RCDC_OK;
 }
@@ -587,122 +542,122 @@ rcdc_status rcdc_prune_mark(rcdc_prune *pr, uint8_t *d_counts, uint8_t *d_used,
     const uint64_t n = pr->n, m = pr->m, np = pr->n_packs;
     if ((m && !d_counts) || (n && !d_used) || (np && !packs))
         return invalid("rcdc_prune_mark: null array");
-    Guard g(pr->device);
+    DeviceGuard g(pr->device);
     hipStream_t st = (hipStream_t)hip_stream;
     const PrView v = view_of(pr);
 
     // scalars: [0] missing, [1] dup entries, [2] compaction cursor, [3] unsettled,
     // [4] (as uint32) first missing
-    PR_TRY(pr->scalars.need(5 * 8));
-    unsigned long long *sc = pr->scalars.as<unsigned long long>();
+    if (rcdc_status rs = pr->scalars.ensure(5, true)) return rs;
+    unsigned long long *sc = pr->scalars;
     uint32_t *first_missing = reinterpret_cast<uint32_t *>(sc + 4);
-    PR_TRY(pr->cnt.need(std::max<uint64_t>(m, 1) * 4));
-    PR_TRY(pr->taken.need(std::max<uint64_t>(m, 1) * 4));
-    PR_TRY(pr->state.need(std::max<uint64_t>(np, 1) * 4));
-    PR_TRY(pr->pending.need(std::max<uint64_t>(np, 1) * 4));
-    PR_TRY(pr->trigger.need(std::max<uint64_t>(np, 1) * 4));
-    PR_TRY(pr->packs_out.need(std::max<uint64_t>(np, 1) * sizeof(rcdc_prune_pack)));
-    uint32_t *cnt = pr->cnt.as<uint32_t>(), *taken = pr->taken.as<uint32_t>();
-    uint32_t *state = pr->state.as<uint32_t>(), *pending = pr->pending.as<uint32_t>();
-    uint32_t *trigger = pr->trigger.as<uint32_t>();
+    if (rcdc_status rs = pr->cnt.ensure(std::max<uint64_t>(m, 1), true)) return rs;
+    if (rcdc_status rs = pr->taken.ensure(std::max<uint64_t>(m, 1), true)) return rs;
+    if (rcdc_status rs = pr->state.ensure(std::max<uint64_t>(np, 1), true)) return rs;
+    if (rcdc_status rs = pr->pending.ensure(std::max<uint64_t>(np, 1), true)) return rs;
+    if (rcdc_status rs = pr->trigger.ensure(std::max<uint64_t>(np, 1), true)) return rs;
+    if (rcdc_status rs = pr->packs_out.ensure(std::max<uint64_t>(np, 1), true)) return rs;
+    uint32_t *cnt = pr->cnt, *taken = pr->taken;
+    uint32_t *state = pr->state, *pending = pr->pending;
+    uint32_t *trigger = pr->trigger;
 
-    PR_TRY(hipEventRecord(pr->ev[0], st));
-    PR_TRY(hipMemsetAsync(sc, 0, 4 * 8, st));
-    PR_TRY(hipMemsetAsync(sc + 4, 0xFF, 8, st));
+    HIP_TRY(hipEventRecord(pr->ev[0], st));
+    HIP_TRY(hipMemsetAsync(sc, 0, 4 * 8, st));
+    HIP_TRY(hipMemsetAsync(sc + 4, 0xFF, 8, st));
     if (m) {
-        PR_TRY(hipMemsetAsync(cnt, 0, m * 4, st));
-        PR_TRY(hipMemsetAsync(taken, 0xFF, m * 4, st));
+        HIP_TRY(hipMemsetAsync(cnt, 0, m * 4, st));
+        HIP_TRY(hipMemsetAsync(taken, 0xFF, m * 4, st));
     }
     if (np) {
-        PR_TRY(hipMemsetAsync(state, 0, np * 4, st));
-        PR_TRY(hipMemsetAsync(pending, 0, np * 4, st));
-        PR_TRY(hipMemsetAsync(trigger, 0xFF, np * 4, st));
+        HIP_TRY(hipMemsetAsync(state, 0, np * 4, st));
+        HIP_TRY(hipMemsetAsync(pending, 0, np * 4, st));
+        HIP_TRY(hipMemsetAsync(trigger, 0xFF, np * 4, st));
     }
     if (n) {
         hipLaunchKernelGGL(rcdc_pr_count_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, st, v, cnt);
-        PR_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (m) {
         hipLaunchKernelGGL(rcdc_pr_counts_out_kernel, dim3(blocks_for(m)), dim3(kBlock), 0, st, cnt,
                            m, d_counts, sc, first_missing);
-        PR_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (n) {
         hipLaunchKernelGGL(rcdc_pr_singles_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, st, v, cnt,
                            d_used, state, trigger, sc + 1);
-        PR_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     unsigned long long host_sc[5];
-    PR_TRY(hipMemcpyAsync(host_sc, sc, sizeof host_sc, hipMemcpyDeviceToHost, st));
-    PR_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(host_sc, sc, sizeof host_sc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     const uint64_t nd = host_sc[1];
     uint32_t rounds = 0;
     if (nd) {
-        PR_TRY(pr->keys_a.need(nd * 8));
-        PR_TRY(pr->keys_b.need(nd * 8));
-        PR_TRY(pr->vals_a.need(nd * 4));
-        PR_TRY(pr->vals_b.need(nd * 4));
-        PR_TRY(pr->progress.need(nd * 4));
-        uint64_t *ka = pr->keys_a.as<uint64_t>(), *kb = pr->keys_b.as<uint64_t>();
-        uint32_t *va = pr->vals_a.as<uint32_t>(), *vb = pr->vals_b.as<uint32_t>();
+        if (rcdc_status rs = pr->keys_a.ensure(nd, true)) return rs;
+        if (rcdc_status rs = pr->keys_b.ensure(nd, true)) return rs;
+        if (rcdc_status rs = pr->vals_a.ensure(nd, true)) return rs;
+        if (rcdc_status rs = pr->vals_b.ensure(nd, true)) return rs;
+        if (rcdc_status rs = pr->progress.ensure(nd, true)) return rs;
+        uint64_t *ka = pr->keys_a, *kb = pr->keys_b;
+        uint32_t *va = pr->vals_a, *vb = pr->vals_b;
         hipLaunchKernelGGL(rcdc_pr_compact_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, st, v, cnt,
                            sc + 2, nd, ka, va);
-        PR_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         size_t tmp = 0;
-        PR_TRY(rocprim::radix_sort_pairs(nullptr, tmp, ka, kb, va, vb, (size_t)nd, 0u, 64u, st));
-        PR_TRY(pr->sort_tmp.need(std::max<uint64_t>(tmp, 1)));
-        PR_TRY(rocprim::radix_sort_pairs(pr->sort_tmp.p, tmp, ka, kb, va, vb, (size_t)nd, 0u, 64u,
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, ka, kb, va, vb, (size_t)nd, 0u, 64u, st));
+        if (rcdc_status rs = pr->sort_tmp.ensure(std::max<uint64_t>(tmp, 1), true)) return rs;
+        HIP_TRY(rocprim::radix_sort_pairs(pr->sort_tmp, tmp, ka, kb, va, vb, (size_t)nd, 0u, 64u,
                                          st));
-        PR_TRY(hipMemsetAsync(pr->progress.p, 0, nd * 4, st));
+        HIP_TRY(hipMemsetAsync(pr->progress, 0, nd * 4, st));
         hipLaunchKernelGGL(rcdc_pr_pending_kernel, dim3(blocks_for(nd)), dim3(kBlock), 0, st, v, kb,
                            vb, nd, cnt, pending);
-        PR_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (np) {
         hipLaunchKernelGGL(rcdc_pr_idle_packs_kernel, dim3(blocks_for(np)), dim3(kBlock), 0, st, np,
                            pending, state);
-        PR_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (nd) {
-        const uint64_t *kb = pr->keys_b.as<uint64_t>();
-        const uint32_t *vb = pr->vals_b.as<uint32_t>();
+        const uint64_t *kb = pr->keys_b;
+        const uint32_t *vb = pr->vals_b;
         for (;;) {
             if (rounds > np)  // n_packs + 1 rounds have run and ids are still unsettled
                 return rcdc::set_error(RCDC_ERR_INTERNAL,
                                        "rcdc_prune_mark: the marking did not settle");
-            PR_TRY(hipMemsetAsync(sc + 3, 0, 8, st));
+            HIP_TRY(hipMemsetAsync(sc + 3, 0, 8, st));
             hipLaunchKernelGGL(rcdc_pr_round_kernel, dim3(blocks_for(nd)), dim3(kBlock), 0, st, v,
-                               kb, vb, nd, cnt, taken, pr->progress.as<uint32_t>(), state, pending,
+                               kb, vb, nd, cnt, taken, pr->progress, state, pending,
                                trigger, sc + 3);
-            PR_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             ++rounds;
             unsigned long long unsettled = 0;
-            PR_TRY(hipMemcpyAsync(&unsettled, sc + 3, 8, hipMemcpyDeviceToHost, st));
-            PR_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpyAsync(&unsettled, sc + 3, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             if (!unsettled) break;
         }
         hipLaunchKernelGGL(rcdc_pr_flags_kernel, dim3(blocks_for(nd)), dim3(kBlock), 0, st, v, kb,
                            vb, nd, taken, trigger, d_used);
-        PR_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    PR_TRY(hipEventRecord(pr->ev[1], st));
+    HIP_TRY(hipEventRecord(pr->ev[1], st));
     if (np) {
         hipLaunchKernelGGL(rcdc_pr_sums_kernel, dim3((uint32_t)((np + 3) / 4)), dim3(kBlock), 0, st,
                            v, d_used, pr->len, pr->len_stride, pr->ulen, pr->ulen_stride,
-                           pr->packs_out.as<rcdc_prune_pack>());
-        PR_TRY(hipGetLastError());
-        PR_TRY(hipMemcpyAsync(packs, pr->packs_out.p, np * sizeof(rcdc_prune_pack),
+                           pr->packs_out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(packs, pr->packs_out, np * sizeof(rcdc_prune_pack),
                               hipMemcpyDeviceToHost, st));
     }
-    PR_TRY(hipEventRecord(pr->ev[2], st));
-    PR_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventRecord(pr->ev[2], st));
+    HIP_TRY(hipStreamSynchronize(st));
     result->missing = host_sc[0];
     result->first_missing = (uint32_t)host_sc[4];
     result->dup_entries = nd;
     result->rounds = rounds;
     result->pad = 0;
-    PR_TRY(hipEventElapsedTime(&result->mark_ms, pr->ev[0], pr->ev[1]));
-    PR_TRY(hipEventElapsedTime(&result->sums_ms, pr->ev[1], pr->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&result->mark_ms, pr->ev[0], pr->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&result->sums_ms, pr->ev[1], pr->ev[2]));
     return RCDC_OK;
 }
 
@@ -727,32 +682,32 @@ rcdc_status rcdc_prune_keep(rcdc_prune *pr, const uint8_t *kinds, const uint32_t
         at += pr->ranges[by_rank[r]].count;
     }
     if (n == 0) return RCDC_OK;
-    Guard g(pr->device);
+    DeviceGuard g(pr->device);
     hipStream_t st = (hipStream_t)hip_stream;
     const PrView v = view_of(pr);
-    PR_TRY(pr->kinds.need(std::max<uint64_t>(np, 1)));
-    PR_TRY(pr->fprefix.need(std::max<uint64_t>(np, 1) * 4));
-    PR_TRY(pr->blocked.need(std::max<uint64_t>(m, 1) * 4));
-    PR_TRY(pr->minpos.need(std::max<uint64_t>(m, 1) * 4));
+    if (rcdc_status rs = pr->kinds.ensure(std::max<uint64_t>(np, 1), true)) return rs;
+    if (rcdc_status rs = pr->fprefix.ensure(std::max<uint64_t>(np, 1), true)) return rs;
+    if (rcdc_status rs = pr->blocked.ensure(std::max<uint64_t>(m, 1), true)) return rs;
+    if (rcdc_status rs = pr->minpos.ensure(std::max<uint64_t>(m, 1), true)) return rs;
     if (np) {
-        PR_TRY(hipMemcpyAsync(pr->kinds.p, kinds, np, hipMemcpyHostToDevice, st));
-        PR_TRY(hipMemcpyAsync(pr->fprefix.p, fprefix.data(), np * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pr->kinds, kinds, np, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pr->fprefix, fprefix.data(), np * 4, hipMemcpyHostToDevice, st));
         // the host vector must outlive its copy (pageable memory is staged
         // before the call returns, but do not rely on it)
-        PR_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     if (m) {
-        PR_TRY(hipMemsetAsync(pr->blocked.p, 0, m * 4, st));
-        PR_TRY(hipMemsetAsync(pr->minpos.p, 0xFF, m * 4, st));
+        HIP_TRY(hipMemsetAsync(pr->blocked, 0, m * 4, st));
+        HIP_TRY(hipMemsetAsync(pr->minpos, 0xFF, m * 4, st));
     }
     hipLaunchKernelGGL(rcdc_pr_keep_a_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, st, v,
-                       pr->kinds.as<uint8_t>(), pr->fprefix.as<uint32_t>(),
-                       pr->blocked.as<uint32_t>(), pr->minpos.as<uint32_t>());
-    PR_TRY(hipGetLastError());
+                       pr->kinds, pr->fprefix,
+                       pr->blocked, pr->minpos);
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(rcdc_pr_keep_b_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, st, v,
-                       pr->kinds.as<uint8_t>(), pr->fprefix.as<uint32_t>(),
-                       pr->blocked.as<uint32_t>(), pr->minpos.as<uint32_t>(), d_keep);
-    PR_TRY(hipGetLastError());
+                       pr->kinds, pr->fprefix,
+                       pr->blocked, pr->minpos, d_keep);
+    HIP_TRY(hipGetLastError());
     return RCDC_OK;
 }
 

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rcdc_internal.h"
+#include "rcdc_launch.h"
 
 using namespace rcdc;
 

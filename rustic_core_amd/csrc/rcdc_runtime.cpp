@@ -27,95 +27,10 @@
 #include <vector>
 
 #include "../../include/rcdc.h"
+#include "rcdc_host.h"
 #include "rcdc_internal.h"
+#include "rcdc_launch.h"
 #include "rcdc_place.h"
-
-namespace rcdc {
-int scan_threads(int code);
-hipError_t launch_scan(int code, const uint8_t *arena, const ScanItem *items, uint32_t nitems,
-                       const uint64_t *gtab, const ScanParams &prm, uint4 *sums,
-                       uint64_t *item_masks, uint32_t blocks, hipStream_t stream);
-hipError_t launch_resolve(const uint8_t *arena, const StreamDesc *sds, const ResolveUnit *units,
-                          uint32_t nunits, const StitchDesc *stitches, uint32_t nstitch,
-                          const uint64_t *gtab, const ResolveParams &prm, const uint4 *sums,
-                          const uint64_t *item_masks, uint64_t *cuts, uint64_t *counts,
-                          uint64_t *piece_cuts, uint64_t *piece_counts, uint64_t *stats,
-                          hipStream_t stream);
-hipError_t launch_window(const uint64_t *cuts, const uint64_t *counts, uint32_t stream,
-                         uint64_t base, uint64_t bound, uint32_t k, uint64_t *out,
-                         hipStream_t hs);
-bool host_sha_supported();
-void host_sha256_many(const uint8_t *const *ptrs, const uint64_t *lens, uint32_t n,
-                      uint8_t *digests);
-hipError_t launch_walk(const uint8_t *arena, const StreamDesc *sds, const WalkUnit *units,
-                       const WalkParams &prm, const uint64_t *gtab, uint64_t *piece_cuts,
-                       uint64_t *pstatus, uint32_t *ctr, uint32_t blocks, hipStream_t stream,
-                       bool ordered);
-hipError_t launch_walk_order(const uint8_t *arena, const StreamDesc *sds, const WalkUnit *units,
-                             const WalkParams &prm, hipStream_t stream);
-hipError_t launch_walk_chain(const uint8_t *arena, const StreamDesc *sds, const WalkUnit *units,
-                             const uint32_t *stream_unit0, uint32_t nstreams,
-                             const WalkParams &prm, const uint64_t *gtab,
-                             const uint64_t *piece_cuts, const uint64_t *pstatus, BoundRes *bres,
-                             uint32_t *ctr, uint32_t *fixlist, uint64_t *fix_cuts,
-                             FixRes *fixres, uint64_t *cuts, uint64_t *counts,
-                             uint32_t fix_blocks, uint32_t chk_cap, hipStream_t stream,
-                             bool wide);
-hipError_t launch_sha256_list(const uint8_t *arena, const ulonglong2 *refs, uint32_t n,
-                              uint32_t *digests, hipStream_t stream);
-hipError_t launch_sha256_plan(const uint8_t *arena, const StreamDesc *sds, uint32_t nstreams,
-                              const uint64_t *cuts, const uint64_t *counts, uint64_t nslots,
-                              uint64_t max_len, uint32_t *bwork, uint32_t *order,
-                              uint32_t *digests, hipStream_t stream);
-hipError_t launch_sha256_multi(uint32_t n, const uint8_t *const *arenas,
-                               const StreamDesc *const *sds, const uint32_t *nstreams,
-                               const uint64_t *const *cuts, const uint64_t *const *counts,
-                               const uint64_t *nslots, uint64_t max_len, uint32_t *const *bwork,
-                               uint32_t *const *order, uint32_t *const *digests,
-                               hipStream_t stream);
-hipError_t launch_aead(bool open, const uint8_t *in, uint8_t *out, const AeadBlob *blobs,
-                       uint32_t nblobs, const AeadUnit *units, uint32_t nunits,
-                       const uint32_t *unit0, const AeadKeyDev *key, uint32_t *partials,
-                       uint32_t *status, uint32_t cus, hipStream_t stream);
-uint32_t zstd_block_grid(uint32_t cus, int level);
-uint64_t zstd_far_words(int level, uint64_t nblk);
-void zstd_prof_dump();
-void zstd_check_prof_dump();
-hipError_t launch_zstd(const uint8_t *in, uint8_t *out, const ZstdBlob *blobs, uint32_t nblobs,
-                       const ZstdBlk *blks, uint32_t nblk, const ZstdTables *tabs, uint8_t *slots,
-                       uint64_t *seqbuf, uint32_t grid, uint2 *res, uint64_t *bpos,
-                       uint64_t *out_lens, uint32_t *queue, uint32_t *far, int level,
-                       hipStream_t stream);
-uint64_t zstd_check_scratch_bytes(uint32_t grid);
-uint64_t zstd_blkdesc_bytes();
-uint32_t zstd_check_waves_per_cu();
-hipError_t launch_zstd_check_blocks(const uint8_t *frames, const uint8_t *data, const void *refs,
-                                    const uint64_t *blk0, uint32_t n, void *blks, uint64_t nblk,
-                                    uint8_t *scratch, uint32_t grid, uint32_t *status,
-                                    uint32_t *ctr, hipStream_t stream);
-uint32_t zdx_waves_per_cu();
-hipError_t launch_zdx_blocks(const uint8_t *frames, const void *refs, uint32_t n, bool write,
-                             bool all_in_order, const ZdxPlace *place, const ZdxLayout &lay,
-                             uint8_t *ws, ZdxFrame *frm, hipStream_t stream);
-hipError_t launch_zdx_entropy(const uint8_t *frames, const ZdxFrame *frm, const ZdxLayout &lay,
-                              uint8_t *ws, uint64_t nblk, uint32_t grid, uint32_t *ctr,
-                              hipStream_t stream);
-hipError_t launch_zdx_inorder(const uint8_t *frames, const ZdxFrame *frm, const ZdxPlace *place,
-                              const uint32_t *list, uint32_t nlist, const ZdxLayout &lay, uint8_t *ws,
-                              uint32_t grid, uint32_t *ctr, hipStream_t stream);
-hipError_t launch_zdx_copy(const uint8_t *frames, const void *refs, const ZdxFrame *frm,
-                           const ZdxPlace *place, const uint32_t *order, uint32_t nlist,
-                           const ZdxLayout &lay, uint8_t *ws, uint8_t *d_out, uint64_t *out_lens,
-                           uint32_t *status, uint32_t grid, uint32_t *ctr, hipStream_t stream);
-hipError_t launch_plan_set_len(StreamDesc *sds, ScanItem *items, uint32_t nitems, uint64_t n,
-                               uint64_t nseg, hipStream_t stream);
-hipError_t launch_copy_ranges(uint8_t *out, const void *units, uint32_t n, uint32_t cus,
-                              hipStream_t stream);
-hipError_t launch_zstd_check(const uint8_t *frames, const uint8_t *data, const void *refs,
-                             const uint32_t *order, uint32_t n, bool stored, uint8_t *scratch,
-                             uint32_t grid,
-                             uint32_t *status, uint32_t *ctr, hipStream_t stream);
-}  // namespace rcdc
 
 using namespace rcdc;
 
@@ -134,13 +49,6 @@ rcdc_status fail(rcdc_status st, const char *fmt, ...) {
     g_err = buf;
     return st;
 }
-
-#define HIP_TRY(expr)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return fail(RCDC_ERR_INTERNAL, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // ---------------------------------------------------------------------------
 // GF(2) polynomial arithmetic for the Rabin64 tables (rustic_cdc Polynom64)
@@ -176,6 +84,35 @@ uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 // ---------------------------------------------------------------------------
 // context / plan objects
 // ---------------------------------------------------------------------------
+// What exists once per run in flight: the buffers one run's hashing kernels
+// (scan, walk) write and its chain kernels (resolve, check, fixup, assemble)
+// read, and what orders the two.  A plan runs on set 0; a pipelined plan
+// (rcdc_plan_set_pipeline) alternates between sets 0 and 1.  Sized and
+// cleared by plan_size_set.
+struct WalkSet {
+    DevBuf<uint4> sums;      // scan summaries
+    DevBuf<uint64_t> masks;  // per scan item
+    DevBuf<uint64_t> wpiece, pstatus;  // walk piece cuts and status
+    DevBuf<uint64_t> wstate;           // WalkParams.wstate
+    DevBuf<BoundRes> bres;
+    DevBuf<uint32_t> ctr;
+    DevBuf<uint32_t> fixlist;
+    DevBuf<uint64_t> fixcuts;
+    DevBuf<FixRes> fixres;
+    // kWalkStats work counters.  Set 0: four slots (WalkParams.stats_next),
+    // of which slot 0 is also its single buffer when counters are reset by
+    // memsets; set 1: one slot, used only without kWalkKReset
+    DevBuf<unsigned long long> wstats;
+    // walk queue order.  Set 0: the plan's static order, then (cost
+    // ordering) this set's sorted order and one key byte per piece; set 1:
+    // its sorted order and key bytes only
+    DevBuf<uint32_t> worder;
+    uint32_t qbase = 0;  // walk queue counter at the set's next run (WalkParams.qbase)
+    hipStream_t hstream = nullptr;  // hashing stream of a pipelined run
+    hipEvent_t ev_in = nullptr, ev_scan = nullptr, ev_res = nullptr;
+    bool res_pending = false;
+};
+
 struct rcdc_plan {
     rcdc_ctx *ctx = nullptr;
     uint32_t n = 0;
@@ -193,19 +130,14 @@ struct rcdc_plan {
     std::vector<StitchDesc> stitches;
     uint64_t npiece_cuts = 0;
     // device
-    ScanItem *d_items = nullptr;
-    StreamDesc *d_sds = nullptr;
-    ResolveUnit *d_units = nullptr;
-    StitchDesc *d_stitches = nullptr;
-    uint64_t *d_piece_cuts = nullptr;
-    uint64_t *d_piece_counts = nullptr;
-    uint64_t cap_units = 0, cap_stitches = 0, cap_piece_cuts = 0, cap_piece_counts = 0;
-    uint4 *d_sums = nullptr;
-    uint64_t *d_masks = nullptr;
-    uint64_t *d_cuts = nullptr;
-    uint64_t *d_counts = nullptr;
-    uint64_t cap_items = 0, cap_sds = 0, cap_sums = 0, cap_cuts = 0, cap_masks = 0,
-             cap_counts = 0;
+    DevBuf<ScanItem> d_items;
+    DevBuf<StreamDesc> d_sds;
+    DevBuf<ResolveUnit> d_units;
+    DevBuf<StitchDesc> d_stitches;
+    DevBuf<uint64_t> d_piece_cuts;
+    DevBuf<uint64_t> d_piece_counts;
+    DevBuf<uint64_t> d_cuts;
+    DevBuf<uint64_t> d_counts;
     // walk path (long streams, rcdc_walk.hip)
     bool no_walk = false;             // force the scan path (fallback re-runs)
     bool no_pieces = false;           // one resolve unit per stream (capacity plans)
@@ -214,30 +146,15 @@ struct rcdc_plan {
     std::vector<uint32_t> worder;      // walk queue order (big pieces first)
     uint32_t nsmall_units = 0;         // the split pieces at worder's end
     bool walk_many = false;            // pieces outnumber 2x the wave slots
+    bool walk_cost = false;            // the queue is cost-sorted on every run
     uint64_t walk_small = 0;           // Ls of the split pieces
     std::vector<uint8_t> walked;       // per stream: on the walk path
     uint64_t nwpiece_cuts = 0;
     WalkParams wprm{};
-    WalkUnit *d_wunits = nullptr;
-    uint32_t *d_wsu0 = nullptr;
-    uint32_t *d_worder = nullptr;
-    uint64_t *d_wpiece = nullptr;
-    uint64_t *d_pstatus = nullptr;
-    uint64_t *d_wstate = nullptr, *d_wstate2 = nullptr;  // WalkParams.wstate of set 0 / 1
-    uint64_t cap_wstate = 0, cap_wstate2 = 0;
+    DevBuf<WalkUnit> d_wunits;
+    DevBuf<uint32_t> d_wsu0;
+    DevBuf<unsigned long long> d_wtrace;  // per-unit trace (RCDC_WALK_TRACE=1)
     uint64_t walk_epoch = 0;  // runs of the walk kernel (WalkParams.epoch)
-    uint32_t wqbase[2] = {0, 0};  // walk queue counter at the next run of set 0 / 1 (WalkParams.qbase)
-    BoundRes *d_bres = nullptr;
-    uint32_t *d_ctr = nullptr;
-    uint32_t *d_fixlist = nullptr;
-    uint64_t *d_fixcuts = nullptr;
-    FixRes *d_fixres = nullptr;
-    unsigned long long *d_wstats = nullptr;  // kWalkStats work counters of the last run
-    unsigned long long *d_wtrace = nullptr;  // per-unit trace (RCDC_WALK_TRACE=1)
-    uint64_t cap_wstats = 0, cap_wtrace = 0;
-    uint64_t cap_worder = 0;
-    uint64_t cap_wunits = 0, cap_wsu0 = 0, cap_wpiece = 0, cap_pstatus = 0, cap_bres = 0,
-             cap_ctr = 0, cap_fixlist = 0, cap_fixcuts = 0, cap_fixres = 0;
     const void *last_arena = nullptr;  // of the last run (fallback re-runs)
     hipStream_t last_stream = nullptr;
     hipEvent_t done = nullptr;
@@ -246,7 +163,8 @@ struct rcdc_plan {
     // walk) go to hashing stream k % 2, its chain kernels (resolve, check,
     // fixup, assemble) to the chain stream.  Hashing k + 1 thus overlaps
     // chain k, and the next walk fills the tail of the previous one.  Every
-    // per-run buffer the chain reads ping-pongs between two sets.
+    // per-run buffer the chain reads ping-pongs between the two sets.
+    WalkSet sets[2];
     bool pipelined = false;
     // boundary-check workgroups of a pipelined run: the check is latency
     // bound and each workgroup holds a whole CU (128 KiB of LDS tables), so
@@ -257,32 +175,13 @@ struct rcdc_plan {
     bool flush_next = false;          // the next pipelined run is the last: its chain runs on
                                       // every CU (rcdc_plan_set_pipeline(plan, 2))
     uint32_t pp = 0;                  // buffer set of the next run
-    uint32_t last_set = 0;            // buffer set of the last run
     uint64_t wruns = 0;               // walk runs (the work-counter slot: wruns % 4)
-    uint32_t last_wslot = 0;          // the last run's work-counter slot
-    uint4 *d_sums2 = nullptr;
-    uint64_t *d_masks2 = nullptr;
-    uint64_t cap_sums2 = 0, cap_masks2 = 0;
+    const unsigned long long *last_wstats = nullptr;  // the work counters the last run wrote
     hipStream_t rstream = nullptr;
-    hipStream_t hstream[2] = {nullptr, nullptr};
-    hipEvent_t ev_in[2] = {nullptr, nullptr};
-    hipEvent_t ev_scan[2] = {nullptr, nullptr};
-    hipEvent_t ev_res[2] = {nullptr, nullptr};
-    bool res_pending[2] = {false, false};
-    // walk buffer set 1 (set 0 is the d_w* fields above)
-    uint64_t *d_wpiece2 = nullptr, *d_pstatus2 = nullptr, *d_fixcuts2 = nullptr;
-    BoundRes *d_bres2 = nullptr;
-    uint32_t *d_ctr2 = nullptr, *d_fixlist2 = nullptr, *d_worder2 = nullptr;
-    FixRes *d_fixres2 = nullptr;
-    unsigned long long *d_wstats2 = nullptr;
-    uint64_t cap_wpiece2 = 0, cap_pstatus2 = 0, cap_fixcuts2 = 0, cap_bres2 = 0, cap_ctr2 = 0,
-             cap_fixlist2 = 0, cap_worder2 = 0, cap_fixres2 = 0, cap_wstats2 = 0;
     // SHA-256 of every chunk (rcdc_plan_hash), slot-indexed like d_cuts
-    uint32_t *d_dig = nullptr;
-    uint64_t cap_dig = 0;
-    uint32_t *d_shaw = nullptr;   // length-bucket counters + total
-    uint32_t *d_order = nullptr;  // slots sorted by chunk length, longest first
-    uint64_t cap_shaw = 0, cap_order = 0;
+    DevBuf<uint32_t> d_dig;
+    DevBuf<uint32_t> d_shaw;   // length-bucket counters + total
+    DevBuf<uint32_t> d_order;  // slots sorted by chunk length, longest first
     bool hashed = false;
     bool finished = false;           // rcdc_plan_finish done for the last run
     std::vector<uint64_t> fin_counts;  // per-stream counts after the finish
@@ -292,6 +191,21 @@ struct rcdc_plan {
     uint64_t tcalls = 0;          // runs since timing was enabled
     std::vector<hipEvent_t> tev;  // 3 per timed run: before scan, after scan, after resolve
     uint64_t truns = 0;
+
+    // Whoever destroys a plan has made its context's device current
+    // (plan_free, plan_finish's temporary): the buffers are freed after this
+    // body, by their own destructors.
+    ~rcdc_plan() {
+        for (WalkSet &S : sets) {
+            if (S.ev_in) (void)hipEventDestroy(S.ev_in);
+            if (S.ev_scan) (void)hipEventDestroy(S.ev_scan);
+            if (S.ev_res) (void)hipEventDestroy(S.ev_res);
+            if (S.hstream) (void)hipStreamDestroy(S.hstream);
+        }
+        if (rstream) (void)hipStreamDestroy(rstream);
+        if (done) (void)hipEventDestroy(done);
+        for (hipEvent_t e : tev) (void)hipEventDestroy(e);
+    }
 };
 
 // One host-buffer worker of a context ("lane"): a HIP stream of its own, two
@@ -305,8 +219,7 @@ struct Lane {
     uint8_t *pinned[4] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t nslots = 2;
     uint64_t stage = 0;  // bytes per staging slot
-    uint8_t *d_arena = nullptr;
-    uint64_t arena_cap = 0;
+    DevBuf<uint8_t> d_arena;
     rcdc_plan *plan = nullptr;
     std::vector<uint64_t> lay_offs, lay_lens;  // layout of the cached plan
     uint64_t lay_arena = 0;
@@ -330,15 +243,13 @@ struct rcdc_ctx {
     std::mutex aead_mu;
     uint8_t aead_key[64] = {0};
     bool aead_key_set = false;
-    AeadKeyDev *d_aead_key = nullptr;
-    AeadBlob *d_aead_blobs = nullptr;
-    AeadUnit *d_aead_units = nullptr;
-    uint32_t *d_aead_unit0 = nullptr, *d_aead_partials = nullptr, *d_aead_status = nullptr;
-    uint8_t *d_aead_stage = nullptr;  // pack headers
+    DevBuf<AeadKeyDev> d_aead_key;
+    DevBuf<AeadBlob> d_aead_blobs;
+    DevBuf<AeadUnit> d_aead_units;
+    DevBuf<uint32_t> d_aead_unit0, d_aead_partials, d_aead_status;
+    DevBuf<uint8_t> d_aead_stage;  // pack headers
     uint8_t *h_aead_up = nullptr;     // page-locked source of a call's uploads
     uint64_t cap_aead_up = 0;
-    uint64_t cap_aead_key = 0, cap_aead_blobs = 0, cap_aead_units = 0, cap_aead_unit0 = 0,
-             cap_aead_partials = 0, cap_aead_status = 0, cap_aead_stage = 0;
     hipEvent_t aead_done = nullptr;
     // ordering of calls on the context's stream (hip_stream == 0) with the
     // legacy default stream (null_enter / null_leave)
@@ -350,46 +261,36 @@ struct rcdc_ctx {
     std::vector<uint8_t *> tail_pool, tail_all;
     // blob compression (rcdc_zstd_compress): calls on one context take turns
     std::mutex zstd_mu;
-    ZstdTables *d_zstd_tabs = nullptr;
-    ZstdBlob *d_zstd_blobs = nullptr;
-    ZstdBlk *d_zstd_blks = nullptr;
-    uint2 *d_zstd_res = nullptr;
-    uint64_t *d_zstd_bpos = nullptr, *d_zstd_lens = nullptr, *d_zstd_seq = nullptr;
-    uint32_t *d_zstd_queue = nullptr;  // per window: blocks taken past the first grid
-    uint64_t cap_zstd_queue = 0;
-    uint8_t *d_zstd_slots = nullptr;
-    uint32_t *d_zstd_far = nullptr;  // far candidates: tables + maps per block (levels >= 3)
-    uint64_t cap_zstd_far = 0;
-    uint64_t cap_zstd_tabs = 0, cap_zstd_blobs = 0, cap_zstd_blks = 0, cap_zstd_res = 0,
-             cap_zstd_bpos = 0, cap_zstd_lens = 0, cap_zstd_seq = 0, cap_zstd_slots = 0;
+    DevBuf<ZstdTables> d_zstd_tabs;
+    DevBuf<ZstdBlob> d_zstd_blobs;
+    DevBuf<ZstdBlk> d_zstd_blks;
+    DevBuf<uint2> d_zstd_res;
+    DevBuf<uint64_t> d_zstd_bpos, d_zstd_lens, d_zstd_seq;
+    DevBuf<uint32_t> d_zstd_queue;  // per window: blocks taken past the first grid
+    DevBuf<uint8_t> d_zstd_slots;
+    DevBuf<uint32_t> d_zstd_far;  // far candidates: tables + maps per block (levels >= 3)
     // frame checks (rcdc_zstd_check): calls on one context take turns
     std::mutex zck_mu;
-    uint64_t *d_zck_refs = nullptr;
-    uint32_t *d_zck_order = nullptr, *d_zck_status = nullptr;
-    uint8_t *d_zck_scratch = nullptr;
-    uint64_t cap_zck_refs = 0, cap_zck_order = 0, cap_zck_status = 0, cap_zck_scratch = 0;
-    uint64_t *d_zck_blk0 = nullptr;  // block-parallel pass: per-frame block slots
-    uint8_t *d_zck_blks = nullptr;
-    uint64_t cap_zck_blk0 = 0, cap_zck_blks = 0;
+    DevBuf<uint64_t> d_zck_refs;
+    DevBuf<uint32_t> d_zck_order, d_zck_status;
+    DevBuf<uint8_t> d_zck_scratch;
+    DevBuf<uint64_t> d_zck_blk0;  // block-parallel pass: per-frame block slots
+    DevBuf<uint8_t> d_zck_blks;
     // frame decompression (rcdc_zstd_decompress): calls on one context take turns
     std::mutex zdx_mu;
-    uint64_t *d_zdx_refs = nullptr, *d_zdx_lens = nullptr;
-    ZdxFrame *d_zdx_frm = nullptr;
-    ZdxPlace *d_zdx_place = nullptr;
-    uint32_t *d_zdx_order = nullptr, *d_zdx_status = nullptr;
-    uint8_t *d_zdx_ws = nullptr;  // the workspace (ZdxLayout)
-    uint64_t cap_zdx_refs = 0, cap_zdx_lens = 0, cap_zdx_frm = 0, cap_zdx_place = 0,
-             cap_zdx_order = 0, cap_zdx_status = 0, cap_zdx_ws = 0;
+    DevBuf<uint64_t> d_zdx_refs, d_zdx_lens;
+    DevBuf<ZdxFrame> d_zdx_frm;
+    DevBuf<ZdxPlace> d_zdx_place;
+    DevBuf<uint32_t> d_zdx_order, d_zdx_status;
+    DevBuf<uint8_t> d_zdx_ws;  // the workspace (ZdxLayout)
     uint64_t zdx_stats[8] = {0};  // the last call's counters (rcdc_zstd_decompress_stats)
     // pack files from sealed blobs (rcdc_pack_build_raw): copy units
-    uint64_t *d_copy_units = nullptr;
-    uint64_t cap_copy_units = 0;
+    DevBuf<uint64_t> d_copy_units;
     // blobs placed into files (rcdc_place_blobs): calls on one context take turns
     std::mutex place_mu;
-    PlaceTile *d_place_tiles = nullptr;
-    uint64_t *d_place_dests = nullptr;
-    uint32_t *d_place_nz = nullptr;
-    uint64_t cap_place_tiles = 0, cap_place_dests = 0, cap_place_nz = 0;
+    DevBuf<PlaceTile> d_place_tiles;
+    DevBuf<uint64_t> d_place_dests;
+    DevBuf<uint32_t> d_place_nz;
     uint8_t *h_place = nullptr;  // page-locked: destination addresses, read-back, tiles
     uint64_t cap_h_place = 0;
     // tile windows are uploaded on a stream of their own, so that window
@@ -414,15 +315,6 @@ struct rcdc_stream {
 };
 
 namespace {
-
-struct DeviceGuard {
-    int prev = 0;
-    explicit DeviceGuard(int dev) {
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
 
 // hip_stream == 0 selects the context's own stream.  That stream is created
 // non-blocking, so on its own it is not ordered with the legacy default
@@ -492,29 +384,6 @@ hipError_t poll_stream(hipStream_t st) {
     }
     if ((e = hipEventRecord(ev, st)) != hipSuccess) return e;
     return poll_event(ev);
-}
-
-// Device buffer of at least `need` elements.  Grows with 25 % headroom: a
-// reallocation's hipFree synchronises the whole device (every lane of every
-// thread), so slowly varying sizes (stream passes of batch + tail bytes)
-// must not reallocate each time.
-template <typename T>
-rcdc_status ensure_dev(T **p, uint64_t *cap, uint64_t need) {
-    if (need <= *cap && *p) return RCDC_OK;
-    static const bool log = getenv("RCDC_ALLOC_LOG") != nullptr;
-    if (log && *p)
-        fprintf(stderr, "rcdc: regrow %llu -> %llu x %zu B (hipFree: device sync)\n",
-                (unsigned long long)*cap, (unsigned long long)need, sizeof(T));
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    // at least 64 KiB: small per-stream arrays (walk streams, piece cuts)
-    // otherwise regrew from 1-2 elements when a layout first had more of
-    // them, each regrow a device-wide sync inside a pipeline (r5u)
-    const uint64_t n = std::max<uint64_t>(need + need / 4, std::max<uint64_t>(65536 / sizeof(T), 1));
-    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return RCDC_OK;
 }
 
 // Choose the per-lane segment S (multiple of 128 in [512, 4096]): the scan
@@ -643,6 +512,49 @@ static uint64_t walk_piece_bytes(const uint64_t *lens, uint32_t n, uint64_t mn, 
         if (lens[i] >= 2 * lp) walkable += lens[i];
     if (walkable / lp < min_pieces) return 0;
     return lp;
+}
+
+// Sizes buffer set k of a built plan and clears what a first run expects
+// cleared; work on `up` (nullptr: synchronous).  plan_build calls it for set
+// 0, and for set 1 once rcdc_plan_set_pipeline has allocated that set, so a
+// rebuild of a pipelined plan sizes both sets.  The two sets differ only in
+// their order and work-counter buffers (WalkSet).
+rcdc_status plan_size_set(rcdc_plan *pl, uint32_t k, hipStream_t up) {
+    WalkSet &S = pl->sets[k];
+    auto clear = [up](void *p, size_t bytes) {
+        return up ? hipMemsetAsync(p, 0, bytes, up) : hipMemset(p, 0, bytes);
+    };
+    rcdc_status st;
+    if ((st = S.sums.ensure(pl->nseg))) return st;
+    if ((st = S.masks.ensure(pl->items.size()))) return st;
+    const uint64_t nw = pl->wunits.size();
+    if (!nw) return RCDC_OK;
+    const uint64_t sorted = pl->walk_cost ? nw + (nw + 3) / 4 : 0;  // the order and its key bytes
+    if (k == 0) {
+        if ((st = S.worder.ensure(nw + sorted))) return st;
+        HIP_TRY(up ? hipMemcpyAsync(S.worder, pl->worder.data(), nw * sizeof(uint32_t),
+                                    hipMemcpyHostToDevice, up)
+                   : hipMemcpy(S.worder, pl->worder.data(), nw * sizeof(uint32_t),
+                               hipMemcpyHostToDevice));
+        if ((st = S.wstats.ensure(4 * kWalkStats))) return st;
+        HIP_TRY(clear(S.wstats, 4 * kWalkStats * 8));
+    } else {
+        if (sorted && (st = S.worder.ensure(sorted))) return st;
+        if ((st = S.wstats.ensure(kWalkStats))) return st;
+    }
+    if ((st = S.wpiece.ensure(pl->nwpiece_cuts))) return st;
+    if ((st = S.pstatus.ensure(nw))) return st;
+    if ((st = S.wstate.ensure(2 * nw))) return st;
+    // epoch 0 = no run (a rebuilt plan keeps counting its runs)
+    HIP_TRY(clear(S.wstate, 2 * nw * 8));
+    if ((st = S.bres.ensure(nw))) return st;
+    if ((st = S.ctr.ensure(4))) return st;
+    HIP_TRY(clear(S.ctr, 16));
+    S.qbase = 0;
+    if ((st = S.fixlist.ensure(nw))) return st;
+    if ((st = S.fixcuts.ensure(nw * pl->wprm.fix_cap))) return st;
+    if ((st = S.fixres.ensure(nw))) return st;
+    return RCDC_OK;
 }
 
 // up: the stream the work lists are uploaded on (nullptr: synchronous copies).
@@ -853,63 +765,32 @@ rcdc_status plan_build(rcdc_ctx *ctx, rcdc_plan *pl, const uint64_t *offs, const
                   : hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
     };
     rcdc_status st;
-    if ((st = ensure_dev(&pl->d_items, &pl->cap_items, pl->items.size()))) return st;
-    if ((st = ensure_dev(&pl->d_sds, &pl->cap_sds, n))) return st;
-    if ((st = ensure_dev(&pl->d_sums, &pl->cap_sums, nseg))) return st;
-    if ((st = ensure_dev(&pl->d_masks, &pl->cap_masks, pl->items.size()))) return st;
-    if ((st = ensure_dev(&pl->d_cuts, &pl->cap_cuts, ncut))) return st;
-    if ((st = ensure_dev(&pl->d_counts, &pl->cap_counts, n))) return st;
-    if ((st = ensure_dev(&pl->d_units, &pl->cap_units, pl->units.size()))) return st;
-    if ((st = ensure_dev(&pl->d_stitches, &pl->cap_stitches, pl->stitches.size()))) return st;
-    if ((st = ensure_dev(&pl->d_piece_cuts, &pl->cap_piece_cuts, pl->npiece_cuts))) return st;
-    if ((st = ensure_dev(&pl->d_piece_counts, &pl->cap_piece_counts, pl->units.size()))) return st;
+    if ((st = pl->d_items.ensure(pl->items.size()))) return st;
+    if ((st = pl->d_sds.ensure(n))) return st;
     const uint64_t nw = pl->wunits.size();
+    // the queue is cost-sorted only when waves take several pieces each: with
+    // about one piece per wave slot the order hardly matters and the two
+    // extra launches are most of C5's latency-bound step
+    pl->walk_cost = nw && pl->walk_many;
+    if (const char *e = getenv("RCDC_WALK_COSTSORT"); e && nw) pl->walk_cost = atoi(e) != 0;
+    // (the sets here, before the cut arrays: a scan plan's allocations keep
+    // the order they have always had)
+    if ((st = plan_size_set(pl, 0, up))) return st;
+    if (pl->sets[1].sums && (st = plan_size_set(pl, 1, up))) return st;  // a pipelined plan
+    if ((st = pl->d_cuts.ensure(ncut))) return st;
+    if ((st = pl->d_counts.ensure(n))) return st;
+    if ((st = pl->d_units.ensure(pl->units.size()))) return st;
+    if ((st = pl->d_stitches.ensure(pl->stitches.size()))) return st;
+    if ((st = pl->d_piece_cuts.ensure(pl->npiece_cuts))) return st;
+    if ((st = pl->d_piece_counts.ensure(pl->units.size()))) return st;
     if (nw) {
-        if ((st = ensure_dev(&pl->d_wunits, &pl->cap_wunits, nw))) return st;
-        if ((st = ensure_dev(&pl->d_wsu0, &pl->cap_wsu0, pl->wstream_u0.size()))) return st;
-        // d_worder: the static order, then (cost ordering) the per-run
-        // sorted order and one key byte per piece
-        // (only when waves take several pieces each: with about one piece
-        // per wave slot the order hardly matters and the two extra launches
-        // are most of C5's latency-bound step)
-        bool cost = pl->walk_many;
-        if (const char *e = getenv("RCDC_WALK_COSTSORT")) cost = atoi(e) != 0;
-        if ((st = ensure_dev(&pl->d_worder, &pl->cap_worder, cost ? 2 * nw + (nw + 3) / 4 : nw)))
-            return st;
-        pl->wprm.order = cost ? pl->d_worder + nw : pl->d_worder;
-        pl->wprm.order_in = cost ? pl->d_worder : nullptr;
-        pl->wprm.order_out = cost ? pl->d_worder + nw : nullptr;
+        if ((st = pl->d_wunits.ensure(nw))) return st;
+        if ((st = pl->d_wsu0.ensure(pl->wstream_u0.size()))) return st;
         pl->wprm.nbig_units = (uint32_t)(nw - pl->nsmall_units);
-        HIP_TRY(upload(pl->d_worder, pl->worder.data(), nw * sizeof(uint32_t)));
-        if ((st = ensure_dev(&pl->d_wpiece, &pl->cap_wpiece, pl->nwpiece_cuts))) return st;
-        if ((st = ensure_dev(&pl->d_pstatus, &pl->cap_pstatus, nw))) return st;
-        if ((st = ensure_dev(&pl->d_wstate, &pl->cap_wstate, 2 * nw))) return st;
-        // epoch 0 = no run (a rebuilt plan keeps counting its runs)
-        HIP_TRY(up ? hipMemsetAsync(pl->d_wstate, 0, 2 * nw * 8, up)
-                   : hipMemset(pl->d_wstate, 0, 2 * nw * 8));
-        if (pl->d_wstate2) {
-            if ((st = ensure_dev(&pl->d_wstate2, &pl->cap_wstate2, 2 * nw))) return st;
-            HIP_TRY(up ? hipMemsetAsync(pl->d_wstate2, 0, 2 * nw * 8, up)
-                       : hipMemset(pl->d_wstate2, 0, 2 * nw * 8));
-        }
-        if ((st = ensure_dev(&pl->d_bres, &pl->cap_bres, nw))) return st;
-        if ((st = ensure_dev(&pl->d_ctr, &pl->cap_ctr, 4))) return st;
-        HIP_TRY(up ? hipMemsetAsync(pl->d_ctr, 0, 16, up) : hipMemset(pl->d_ctr, 0, 16));
-        if (pl->d_ctr2) HIP_TRY(up ? hipMemsetAsync(pl->d_ctr2, 0, 16, up) : hipMemset(pl->d_ctr2, 0, 16));
-        pl->wqbase[0] = pl->wqbase[1] = 0;
-        if ((st = ensure_dev(&pl->d_fixlist, &pl->cap_fixlist, nw))) return st;
-        if ((st = ensure_dev(&pl->d_fixcuts, &pl->cap_fixcuts, nw * pl->wprm.fix_cap))) return st;
-        if ((st = ensure_dev(&pl->d_fixres, &pl->cap_fixres, nw))) return st;
-        // four slots of work counters (WalkParams.stats_next); slot 0 is also
-        // the single buffer of set 0 when counters are reset by memsets
-        if ((st = ensure_dev(&pl->d_wstats, &pl->cap_wstats, 4 * kWalkStats))) return st;
-        HIP_TRY(up ? hipMemsetAsync(pl->d_wstats, 0, 4 * kWalkStats * 8, up)
-                   : hipMemset(pl->d_wstats, 0, 4 * kWalkStats * 8));
         pl->wruns = 0;
-        pl->wprm.stats = pl->d_wstats;
         pl->wprm.trace = nullptr;
         if (const char *e = getenv("RCDC_WALK_TRACE"); e && atoi(e) > 0) {
-            if ((st = ensure_dev(&pl->d_wtrace, &pl->cap_wtrace, 2 * nw * kTraceWords))) return st;
+            if ((st = pl->d_wtrace.ensure(2 * nw * kTraceWords))) return st;
             HIP_TRY(hipMemset(pl->d_wtrace, 0, 2 * nw * kTraceWords * 8));
             pl->wprm.trace = pl->d_wtrace;
         }
@@ -956,41 +837,28 @@ rcdc_status plan_run(rcdc_plan *pl, const void *d_arena, hipStream_t stream) {
         pl->truns++;
     }
     const uint32_t set = pl->pipelined ? pl->pp : 0;
-    uint4 *sums = set ? pl->d_sums2 : pl->d_sums;
-    uint64_t *masks = set ? pl->d_masks2 : pl->d_masks;
-    // this run's walk buffers and parameters
+    WalkSet &S = pl->sets[set];
+    // this run's walk parameters
     WalkParams wprm = pl->wprm;
-    uint64_t *wpiece = pl->d_wpiece, *pstatus = pl->d_pstatus, *fixcuts = pl->d_fixcuts;
-    wprm.wstate = wprm.seed ? pl->d_wstate : nullptr;
     pl->walk_epoch = pl->walk_epoch % ((1ull << 21) - 1) + 1;  // 1 .. 2^21 - 1
     wprm.epoch = pl->walk_epoch;
-    BoundRes *bres = pl->d_bres;
-    uint32_t *ctr = pl->d_ctr, *fixlist = pl->d_fixlist;
-    FixRes *fixres = pl->d_fixres;
-    if (set && !pl->wunits.empty()) {
-        const uint64_t nw = pl->wunits.size();
-        wpiece = pl->d_wpiece2;
-        pstatus = pl->d_pstatus2;
-        if (wprm.seed) wprm.wstate = pl->d_wstate2;
-        fixcuts = pl->d_fixcuts2;
-        bres = pl->d_bres2;
-        ctr = pl->d_ctr2;
-        fixlist = pl->d_fixlist2;
-        fixres = pl->d_fixres2;
-        wprm.stats = pl->d_wstats2;
-        if (wprm.order_out) {  // the cost-sorted queue (and its key bytes) of this run
-            wprm.order_out = pl->d_worder2;
-            wprm.order = pl->d_worder2;
+    if (const uint64_t nw = pl->wunits.size()) {
+        wprm.wstate = wprm.seed ? S.wstate.get() : nullptr;
+        wprm.stats = S.wstats;
+        uint32_t *const fixed = pl->sets[0].worder;  // the plan's static order
+        wprm.order = fixed;
+        if (pl->walk_cost) {  // the cost-sorted queue (and its key bytes) of this run
+            wprm.order_in = fixed;
+            wprm.order = wprm.order_out = set ? S.worder.get() : fixed + nw;
         }
-        (void)nw;
     }
     bool ordered = false;  // the walk queue's order already enqueued
     if (pl->pipelined) {
         // hashing on this set's stream, after the caller's earlier work and
         // after the chain that last read this set (run k - 2)
-        HIP_TRY(hipEventRecord(pl->ev_in[set], stream));
-        stream = pl->hstream[set];
-        HIP_TRY(hipStreamWaitEvent(stream, pl->ev_in[set], 0));
+        HIP_TRY(hipEventRecord(S.ev_in, stream));
+        stream = S.hstream;
+        HIP_TRY(hipStreamWaitEvent(stream, S.ev_in, 0));
         // the walk queue's cost order reads only the arena: it need not wait
         // for the chain of run k - 2, and fills CUs the last walk frees
         if (!pl->wunits.empty()) {
@@ -998,12 +866,12 @@ rcdc_status plan_run(rcdc_plan *pl, const void *d_arena, hipStream_t stream) {
                                       stream));
             ordered = true;
         }
-        if (pl->res_pending[set]) HIP_TRY(hipStreamWaitEvent(stream, pl->ev_res[set], 0));
+        if (S.res_pending) HIP_TRY(hipStreamWaitEvent(stream, S.ev_res, 0));
     }
     if (ev) HIP_TRY(hipEventRecord(ev[0], stream));
     HIP_TRY(launch_scan(ctx->variant, (const uint8_t *)d_arena, pl->d_items,
                         pl->run_items ? pl->run_items : (uint32_t)pl->items.size(), ctx->d_tables,
-                        sp, sums, masks, pl->run_items ? pl->run_blocks : pl->blocks, stream));
+                        sp, S.sums, S.masks, pl->run_items ? pl->run_blocks : pl->blocks, stream));
     const uint32_t cus = (uint32_t)std::max(ctx->num_cus, 1);
     static const bool dbg = getenv("RCDC_DEBUG_SYNC") != nullptr;  // stage-by-stage sync
     if (dbg) {
@@ -1015,34 +883,33 @@ rcdc_status plan_run(rcdc_plan *pl, const void *d_arena, hipStream_t stream) {
     const bool narrow = pl->pipelined && !pl->flush_next;
     pl->flush_next = false;
     const uint32_t wblocks = (uint32_t)std::min<uint64_t>(cus, (pl->wunits.size() + 15) / 16);
-    wprm.qbase = pl->wqbase[set];
+    wprm.qbase = S.qbase;
     wprm.stats_next = nullptr;
     if ((wprm.flags & kWalkKReset) && !pl->wunits.empty()) {
         const uint32_t slot = (uint32_t)(pl->wruns % 4);
-        wprm.stats = pl->d_wstats + slot * kWalkStats;
-        wprm.stats_next = pl->d_wstats + ((slot + 2) % 4) * kWalkStats;
-        pl->last_wslot = slot;
+        // the four slots of set 0, whichever set runs
+        wprm.stats = pl->sets[0].wstats + slot * kWalkStats;
+        wprm.stats_next = pl->sets[0].wstats + ((slot + 2) % 4) * kWalkStats;
         pl->wruns++;
-    } else {
-        pl->last_wslot = set ? 4 : 0;  // (4: d_wstats2)
     }
+    pl->last_wstats = wprm.stats;
     HIP_TRY(launch_walk((const uint8_t *)d_arena, pl->d_sds, pl->d_wunits, wprm, ctx->d_tables,
-                        wpiece, pstatus, ctr, wblocks, stream, ordered));
+                        S.wpiece, S.pstatus, S.ctr, wblocks, stream, ordered));
     if (!pl->wunits.empty() && (wprm.flags & kWalkKReset))  // takes of this run: one per
-        pl->wqbase[set] += (uint32_t)pl->wunits.size() +     // piece, one failed per wave;
+        S.qbase += (uint32_t)pl->wunits.size() +     // piece, one failed per wave;
                            ((wprm.flags & kWalkStatic) ? 0u : wblocks * 16u);  // static: nunits
     if (dbg) {
         HIP_TRY(hipStreamSynchronize(stream));
         uint32_t h[4] = {0, 0, 0, 0};
-        if (!pl->wunits.empty()) HIP_TRY(hipMemcpy(h, ctr, 16, hipMemcpyDeviceToHost));
+        if (!pl->wunits.empty()) HIP_TRY(hipMemcpy(h, S.ctr, 16, hipMemcpyDeviceToHost));
         fprintf(stderr, "rcdc: walk done (%zu units; queue %u)\n", pl->wunits.size(), h[0]);
     }
     if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
     const hipStream_t scan_stream = stream;
     if (pl->pipelined) {  // resolve on the plan's own stream, after this scan
-        HIP_TRY(hipEventRecord(pl->ev_scan[set], stream));
+        HIP_TRY(hipEventRecord(S.ev_scan, stream));
         stream = pl->rstream;
-        HIP_TRY(hipStreamWaitEvent(stream, pl->ev_scan[set], 0));
+        HIP_TRY(hipStreamWaitEvent(stream, S.ev_scan, 0));
     }
     ResolveParams rp{};
     rp.min_size = ctx->min;
@@ -1052,8 +919,8 @@ rcdc_status plan_run(rcdc_plan *pl, const void *d_arena, hipStream_t stream) {
     rp.shift = (uint32_t)(ctx->deg - 8);
     HIP_TRY(launch_resolve((const uint8_t *)d_arena, pl->d_sds, pl->d_units,
                            (uint32_t)pl->units.size(), pl->d_stitches,
-                           (uint32_t)pl->stitches.size(), ctx->d_tables, rp, sums,
-                           masks, pl->d_cuts, pl->d_counts, pl->d_piece_cuts,
+                           (uint32_t)pl->stitches.size(), ctx->d_tables, rp, S.sums,
+                           S.masks, pl->d_cuts, pl->d_counts, pl->d_piece_cuts,
                            pl->d_piece_counts, nullptr, stream));
     if (dbg) {
         HIP_TRY(hipStreamSynchronize(stream));
@@ -1061,16 +928,15 @@ rcdc_status plan_run(rcdc_plan *pl, const void *d_arena, hipStream_t stream) {
     }
     HIP_TRY(launch_walk_chain((const uint8_t *)d_arena, pl->d_sds, pl->d_wunits, pl->d_wsu0,
                               (uint32_t)pl->wstream_u0.size(), wprm, ctx->d_tables,
-                              wpiece, pstatus, bres, ctr, fixlist,
-                              fixcuts, fixres, pl->d_cuts, pl->d_counts,
+                              S.wpiece, S.pstatus, S.bres, S.ctr, S.fixlist,
+                              S.fixcuts, S.fixres, pl->d_cuts, pl->d_counts,
                               narrow ? std::min<uint32_t>(cus, pl->fix_blocks_pipe) : cus,
                               narrow ? pl->chk_blocks_pipe : cus, stream,
                               pl->pipelined));
     if (ev) HIP_TRY(hipEventRecord(ev[2], stream));
-    pl->last_set = set;
     if (pl->pipelined) {
-        HIP_TRY(hipEventRecord(pl->ev_res[set], stream));
-        pl->res_pending[set] = true;
+        HIP_TRY(hipEventRecord(S.ev_res, stream));
+        S.res_pending = true;
         pl->pp ^= 1u;
     }
     (void)scan_stream;
@@ -1086,8 +952,6 @@ rcdc_status plan_run(rcdc_plan *pl, const void *d_arena, hipStream_t stream) {
     pl->finished = false;
     return RCDC_OK;
 }
-
-void plan_release(rcdc_plan *pl);
 
 // SHA-256 of (offset, length) refs of the plan's last arena into the plan's
 // digest slots (a stream the walk path handed back to the scan path).
@@ -1109,7 +973,7 @@ rcdc_status launch_list_hash(rcdc_plan *pl, const std::vector<ulonglong2> &refs,
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, out.size(), hipMemcpyDeviceToHost);
     for (size_t r = 0; r < refs.size() && e == hipSuccess; r++)
-        e = hipMemcpy((uint8_t *)pl->d_dig + slots[r] * 32, out.data() + r * 32, 32,
+        e = hipMemcpy((uint8_t *)pl->d_dig.get() + slots[r] * 32, out.data() + r * 32, 32,
                       hipMemcpyHostToDevice);
     (void)hipFree(d_refs);
     (void)hipFree(d_out);
@@ -1145,11 +1009,12 @@ rcdc_status plan_finish(rcdc_plan *pl) {
         std::vector<BoundRes> br(nw);
         std::vector<FixRes> fr(nw);
         std::vector<uint64_t> fc(nw * pl->wprm.fix_cap);
-        HIP_TRY(hipMemcpy(ps.data(), pl->d_pstatus, nw * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(pc.data(), pl->d_wpiece, pc.size() * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(br.data(), pl->d_bres, nw * sizeof(BoundRes), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(fr.data(), pl->d_fixres, nw * sizeof(FixRes), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(fc.data(), pl->d_fixcuts, fc.size() * 8, hipMemcpyDeviceToHost));
+        const WalkSet &S = pl->sets[0];  // (of a serial run)
+        HIP_TRY(hipMemcpy(ps.data(), S.pstatus, nw * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pc.data(), S.wpiece, pc.size() * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(br.data(), S.bres, nw * sizeof(BoundRes), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(fr.data(), S.fixres, nw * sizeof(FixRes), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(fc.data(), S.fixcuts, fc.size() * 8, hipMemcpyDeviceToHost));
         for (size_t u = 0; u < nw; u++) {
             const WalkUnit &U = pl->wunits[u];
             if (U.stream != want) continue;
@@ -1199,7 +1064,6 @@ rcdc_status plan_finish(rcdc_plan *pl) {
             if (c1 && hipMemcpy(redo.data(), tmp.d_cuts, c1 * 8, hipMemcpyDeviceToHost) != hipSuccess)
                 st = fail(RCDC_ERR_INTERNAL, "redo cuts");
         }
-        plan_release(&tmp);
         if (st) return st;
         if (c1) HIP_TRY(hipMemcpy(pl->d_cuts + pl->cut_base[i], redo.data(), c1 * 8,
                                   hipMemcpyHostToDevice));
@@ -1249,60 +1113,9 @@ rcdc_status plan_results(rcdc_plan *pl, uint64_t *cuts, uint64_t cap, uint64_t *
     return RCDC_OK;
 }
 
-void plan_release(rcdc_plan *pl) {
-    DeviceGuard g(pl->ctx ? pl->ctx->device : 0);
-    (void)hipFree(pl->d_wunits);
-    (void)hipFree(pl->d_wsu0);
-    (void)hipFree(pl->d_worder);
-    (void)hipFree(pl->d_wpiece);
-    (void)hipFree(pl->d_pstatus);
-    (void)hipFree(pl->d_bres);
-    (void)hipFree(pl->d_ctr);
-    (void)hipFree(pl->d_fixlist);
-    (void)hipFree(pl->d_fixcuts);
-    (void)hipFree(pl->d_fixres);
-    (void)hipFree(pl->d_wstats);
-    (void)hipFree(pl->d_wtrace);
-    (void)hipFree(pl->d_items);
-    (void)hipFree(pl->d_sds);
-    (void)hipFree(pl->d_sums);
-    (void)hipFree(pl->d_masks);
-    (void)hipFree(pl->d_sums2);
-    (void)hipFree(pl->d_masks2);
-    (void)hipFree(pl->d_wpiece2);
-    (void)hipFree(pl->d_pstatus2);
-    (void)hipFree(pl->d_wstate);
-    (void)hipFree(pl->d_wstate2);
-    (void)hipFree(pl->d_fixcuts2);
-    (void)hipFree(pl->d_bres2);
-    (void)hipFree(pl->d_ctr2);
-    (void)hipFree(pl->d_fixlist2);
-    (void)hipFree(pl->d_worder2);
-    (void)hipFree(pl->d_fixres2);
-    (void)hipFree(pl->d_wstats2);
-    for (int k = 0; k < 2; k++) {
-        if (pl->ev_in[k]) (void)hipEventDestroy(pl->ev_in[k]);
-        if (pl->ev_scan[k]) (void)hipEventDestroy(pl->ev_scan[k]);
-        if (pl->ev_res[k]) (void)hipEventDestroy(pl->ev_res[k]);
-        if (pl->hstream[k]) (void)hipStreamDestroy(pl->hstream[k]);
-    }
-    if (pl->rstream) (void)hipStreamDestroy(pl->rstream);
-    (void)hipFree(pl->d_cuts);
-    (void)hipFree(pl->d_counts);
-    (void)hipFree(pl->d_dig);
-    (void)hipFree(pl->d_shaw);
-    (void)hipFree(pl->d_order);
-    (void)hipFree(pl->d_units);
-    (void)hipFree(pl->d_stitches);
-    (void)hipFree(pl->d_piece_cuts);
-    (void)hipFree(pl->d_piece_counts);
-    if (pl->done) (void)hipEventDestroy(pl->done);
-    for (hipEvent_t e : pl->tev) (void)hipEventDestroy(e);
-}
-
 void plan_free(rcdc_plan *pl) {
     if (!pl) return;
-    plan_release(pl);
+    DeviceGuard g(pl->ctx ? pl->ctx->device : 0);
     delete pl;
 }
 
@@ -1315,7 +1128,7 @@ void lane_free(rcdc_ctx *ctx, Lane *L) {
         if (L->ev[k]) (void)hipEventDestroy(L->ev[k]);
         if (L->pinned[k]) (void)hipHostFree(L->pinned[k]);
     }
-    (void)hipFree(L->d_arena);
+    L->d_arena.release();
     if (L->stream) (void)hipStreamDestroy(L->stream);
     delete L;
 }
@@ -1465,7 +1278,7 @@ rcdc_status run_host_pieces(rcdc_ctx *ctx, Lane *L, const std::vector<uint64_t> 
     const uint64_t karena = cap1 ? round_up(cap1, 256) + 256 : arena_len;
     DeviceGuard g(ctx->device);
     rcdc_status st;
-    if ((st = ensure_dev(&L->d_arena, &L->arena_cap, std::max(arena_len, karena)))) return st;
+    if ((st = L->d_arena.ensure(std::max(arena_len, karena)))) return st;
     if (!L->pinned[0]) {
         L->stage = stage_bytes();
         L->nslots = stage_slots();
@@ -1741,52 +1554,18 @@ void rcdc_ctx_destroy(rcdc_ctx *c) {
         if (c->stream) (void)hipStreamSynchronize(c->stream);
         for (Lane *L : c->lanes) lane_free(c, L);
         (void)hipFree(c->d_tables);
-        (void)hipFree(c->d_aead_key);
-        (void)hipFree(c->d_aead_blobs);
-        (void)hipFree(c->d_aead_units);
-        (void)hipFree(c->d_aead_unit0);
-        (void)hipFree(c->d_aead_partials);
-        (void)hipFree(c->d_aead_status);
-        (void)hipFree(c->d_aead_stage);
         (void)hipHostFree(c->h_aead_up);
         if (c->aead_done) (void)hipEventDestroy(c->aead_done);
         if (c->ev_null_in) (void)hipEventDestroy(c->ev_null_in);
         if (c->ev_null_out) (void)hipEventDestroy(c->ev_null_out);
         for (uint8_t *t : c->tail_all) (void)hipFree(t);
-        (void)hipFree(c->d_zstd_tabs);
-        (void)hipFree(c->d_zstd_blobs);
-        (void)hipFree(c->d_zstd_blks);
-        (void)hipFree(c->d_zstd_res);
-        (void)hipFree(c->d_zstd_bpos);
-        (void)hipFree(c->d_zstd_lens);
-        (void)hipFree(c->d_zstd_queue);
-        (void)hipFree(c->d_zstd_seq);
-        (void)hipFree(c->d_zstd_slots);
-        (void)hipFree(c->d_zstd_far);
-        (void)hipFree(c->d_zck_refs);
-        (void)hipFree(c->d_zck_order);
-        (void)hipFree(c->d_zck_status);
-        (void)hipFree(c->d_zck_scratch);
-        (void)hipFree(c->d_zck_blk0);
-        (void)hipFree(c->d_zck_blks);
-        (void)hipFree(c->d_zdx_refs);
-        (void)hipFree(c->d_zdx_lens);
-        (void)hipFree(c->d_zdx_frm);
-        (void)hipFree(c->d_zdx_place);
-        (void)hipFree(c->d_zdx_order);
-        (void)hipFree(c->d_zdx_status);
-        (void)hipFree(c->d_zdx_ws);
-        (void)hipFree(c->d_copy_units);
-        (void)hipFree(c->d_place_tiles);
-        (void)hipFree(c->d_place_dests);
-        (void)hipFree(c->d_place_nz);
         (void)hipHostFree(c->h_place);
         for (hipEvent_t e : c->place_ev)
             if (e) (void)hipEventDestroy(e);
         if (c->place_up) (void)hipStreamDestroy(c->place_up);
         if (c->stream) (void)hipStreamDestroy(c->stream);
+        delete c;  // its device buffers, with the device still current
     }
-    delete c;
 }
 
 uint64_t rcdc_max_cuts(const rcdc_ctx *c, uint64_t n) { return c ? n / c->min + 1 : 0; }
@@ -1835,8 +1614,8 @@ rcdc_status rcdc_plan_device_results(rcdc_plan *plan, uint64_t *d_cuts, uint64_t
                                      const uint64_t **cut_base) {
     if (!plan || !d_cuts || !d_counts || !cut_base)
         return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-    *d_cuts = (uint64_t)(uintptr_t)plan->d_cuts;
-    *d_counts = (uint64_t)(uintptr_t)plan->d_counts;
+    *d_cuts = (uint64_t)(uintptr_t)plan->d_cuts.get();
+    *d_counts = (uint64_t)(uintptr_t)plan->d_counts.get();
     *cut_base = plan->cut_base.data();
     return RCDC_OK;
 }
@@ -1875,28 +1654,7 @@ rcdc_status rcdc_plan_set_pipeline(rcdc_plan *plan, int enable) {
     DeviceGuard g(plan->ctx->device);
     if (plan->ran) HIP_TRY(hipEventSynchronize(plan->done));  // set 0's buffers are free
     rcdc_status st;
-    if ((st = ensure_dev(&plan->d_sums2, &plan->cap_sums2, std::max<uint64_t>(plan->cap_sums, 1))))
-        return st;
-    if ((st = ensure_dev(&plan->d_masks2, &plan->cap_masks2, std::max<uint64_t>(plan->cap_masks, 1))))
-        return st;
-    if (const uint64_t nw = plan->wunits.size()) {
-        if ((st = ensure_dev(&plan->d_wpiece2, &plan->cap_wpiece2, plan->nwpiece_cuts))) return st;
-        if ((st = ensure_dev(&plan->d_pstatus2, &plan->cap_pstatus2, nw))) return st;
-        if ((st = ensure_dev(&plan->d_wstate2, &plan->cap_wstate2, 2 * nw))) return st;
-        HIP_TRY(hipMemset(plan->d_wstate2, 0, 2 * nw * 8));
-        if ((st = ensure_dev(&plan->d_bres2, &plan->cap_bres2, nw))) return st;
-        if ((st = ensure_dev(&plan->d_ctr2, &plan->cap_ctr2, 4))) return st;
-        HIP_TRY(hipMemset(plan->d_ctr2, 0, 16));
-        plan->wqbase[1] = 0;
-        if ((st = ensure_dev(&plan->d_fixlist2, &plan->cap_fixlist2, nw))) return st;
-        if ((st = ensure_dev(&plan->d_fixcuts2, &plan->cap_fixcuts2, nw * plan->wprm.fix_cap)))
-            return st;
-        if ((st = ensure_dev(&plan->d_fixres2, &plan->cap_fixres2, nw))) return st;
-        if ((st = ensure_dev(&plan->d_wstats2, &plan->cap_wstats2, kWalkStats))) return st;
-        if (plan->wprm.order_out &&
-            (st = ensure_dev(&plan->d_worder2, &plan->cap_worder2, nw + (nw + 3) / 4)))
-            return st;
-    }
+    if ((st = plan_size_set(plan, 1, nullptr))) return st;
     const int prio_mode = getenv("RCDC_PIPE_PRIO") ? atoi(getenv("RCDC_PIPE_PRIO")) : 0;
     int prio_lo = 0, prio_hi = 0;
     if (prio_mode) {
@@ -1911,26 +1669,26 @@ rcdc_status rcdc_plan_set_pipeline(rcdc_plan *plan, int enable) {
             HIP_TRY(hipStreamCreateWithFlags(&plan->rstream, hipStreamNonBlocking));
     }
     for (int k = 0; k < 2; k++) {
-        if (!plan->hstream[k]) {
+        if (!plan->sets[k].hstream) {
             // RCDC_PIPE_PRIO (experiments): the two hashing streams at different
             // priorities, so they sit on different hardware queues and run k + 1's
             // walk can start on the CUs run k's walk frees in its tail
             if (prio_mode == 1 || prio_mode == 2)
-                HIP_TRY(hipStreamCreateWithPriority(&plan->hstream[k], hipStreamNonBlocking,
+                HIP_TRY(hipStreamCreateWithPriority(&plan->sets[k].hstream, hipStreamNonBlocking,
                                                     k ? (prio_mode == 2 ? prio_lo : prio_hi) : prio_lo));
             else if (prio_mode == 4)  // three levels: chain high, the hashing streams low / middle
-                HIP_TRY(hipStreamCreateWithPriority(&plan->hstream[k], hipStreamNonBlocking,
+                HIP_TRY(hipStreamCreateWithPriority(&plan->sets[k].hstream, hipStreamNonBlocking,
                                                     k ? (prio_lo + prio_hi) / 2 : prio_lo));
             else
-                HIP_TRY(hipStreamCreateWithFlags(&plan->hstream[k], hipStreamNonBlocking));
+                HIP_TRY(hipStreamCreateWithFlags(&plan->sets[k].hstream, hipStreamNonBlocking));
         }
-        if (!plan->ev_in[k])
-            HIP_TRY(hipEventCreateWithFlags(&plan->ev_in[k], hipEventDisableTiming));
-        if (!plan->ev_scan[k])
-            HIP_TRY(hipEventCreateWithFlags(&plan->ev_scan[k], hipEventDisableTiming));
-        if (!plan->ev_res[k])
-            HIP_TRY(hipEventCreateWithFlags(&plan->ev_res[k], hipEventDisableTiming));
-        plan->res_pending[k] = false;
+        if (!plan->sets[k].ev_in)
+            HIP_TRY(hipEventCreateWithFlags(&plan->sets[k].ev_in, hipEventDisableTiming));
+        if (!plan->sets[k].ev_scan)
+            HIP_TRY(hipEventCreateWithFlags(&plan->sets[k].ev_scan, hipEventDisableTiming));
+        if (!plan->sets[k].ev_res)
+            HIP_TRY(hipEventCreateWithFlags(&plan->sets[k].ev_res, hipEventDisableTiming));
+        plan->sets[k].res_pending = false;
     }
     plan->pp = 0;
     if (const char *e = getenv("RCDC_CHK_BLOCKS")) plan->chk_blocks_pipe = (uint32_t)std::max(atoi(e), 1);
@@ -1961,10 +1719,7 @@ rcdc_status rcdc_plan_walk_stats(rcdc_plan *plan, uint64_t *stats, uint64_t *tra
     DeviceGuard g(plan->ctx->device);
     HIP_TRY(hipEventSynchronize(plan->done));
     static_assert(RCDC_WALK_STATS == kWalkStats, "stats slots");
-    HIP_TRY(hipMemcpy(stats, plan->last_wslot == 4 ? plan->d_wstats2
-                                                    : plan->d_wstats + plan->last_wslot * kWalkStats,
-                      kWalkStats * 8,
-                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stats, plan->last_wstats, kWalkStats * 8, hipMemcpyDeviceToHost));
     const uint64_t nw = 2 * plan->wunits.size() * kTraceWords;  // walk rows, then check rows
     if (trace && trace_cap && plan->wprm.trace)
         HIP_TRY(hipMemcpy(trace, plan->d_wtrace, std::min(trace_cap, nw) * 8,
@@ -2063,9 +1818,9 @@ rcdc_status rcdc_plan_hash(rcdc_plan *plan, const void *d_arena, void *hip_strea
     hipStream_t st;
     rcdc_status rs;
     if ((rs = null_enter(plan->ctx, hip_stream, &st))) return rs;
-    if ((rs = ensure_dev(&plan->d_dig, &plan->cap_dig, plan->ncuts * 8))) return rs;
-    if ((rs = ensure_dev(&plan->d_shaw, &plan->cap_shaw, 256))) return rs;
-    if ((rs = ensure_dev(&plan->d_order, &plan->cap_order, plan->ncuts))) return rs;
+    if ((rs = plan->d_dig.ensure(plan->ncuts * 8))) return rs;
+    if ((rs = plan->d_shaw.ensure(256))) return rs;
+    if ((rs = plan->d_order.ensure(plan->ncuts))) return rs;
     if (st != plan->last_stream) HIP_TRY(hipStreamWaitEvent(st, plan->done, 0));
     HIP_TRY(launch_sha256_plan((const uint8_t *)d_arena, plan->d_sds, plan->n, plan->d_cuts,
                                plan->d_counts, plan->ncuts, plan->ctx->max, plan->d_shaw,
@@ -2103,9 +1858,9 @@ rcdc_status rcdc_plan_hash_many(rcdc_plan *const *plans, uint32_t n,
     for (uint32_t j = 0; j < n; j++) {
         rcdc_plan *pl = plans[j];
         rcdc_status rs;
-        if ((rs = ensure_dev(&pl->d_dig, &pl->cap_dig, pl->ncuts * 8))) return rs;
-        if ((rs = ensure_dev(&pl->d_shaw, &pl->cap_shaw, 256))) return rs;
-        if ((rs = ensure_dev(&pl->d_order, &pl->cap_order, pl->ncuts))) return rs;
+        if ((rs = pl->d_dig.ensure(pl->ncuts * 8))) return rs;
+        if ((rs = pl->d_shaw.ensure(256))) return rs;
+        if ((rs = pl->d_order.ensure(pl->ncuts))) return rs;
         if (st != pl->last_stream) HIP_TRY(hipStreamWaitEvent(st, pl->done, 0));
         ar[j] = (const uint8_t *)d_arenas[j];
         sd[j] = pl->d_sds;
@@ -2161,7 +1916,7 @@ rcdc_status rcdc_plan_digests(rcdc_plan *plan, uint8_t *digests, uint64_t cap_ch
 rcdc_status rcdc_plan_device_digests(rcdc_plan *plan, uint64_t *d_digests) {
     if (!plan || !d_digests) return fail(RCDC_ERR_INVALID_INPUT, "null argument");
     if (!plan->hashed) return fail(RCDC_ERR_INVALID_INPUT, "rcdc_plan_hash has not been run");
-    *d_digests = (uint64_t)(uintptr_t)plan->d_dig;
+    *d_digests = (uint64_t)(uintptr_t)plan->d_dig.get();
     return RCDC_OK;
 }
 
@@ -2294,7 +2049,7 @@ rcdc_status aead_launch(rcdc_ctx *ctx, bool open, const uint8_t key[64], std::ve
     // (the last call's work is done: every call ends synchronised)
     if (!ctx->aead_done) HIP_TRY(hipEventCreateWithFlags(&ctx->aead_done, hipEventDisableTiming));
     rcdc_status rs;
-    if ((rs = ensure_dev(&ctx->d_aead_key, &ctx->cap_aead_key, 1))) return rs;
+    if ((rs = ctx->d_aead_key.ensure(1))) return rs;
     if (!ctx->aead_key_set || memcmp(ctx->aead_key, key, 64) != 0) {
         AeadKeyDev K;
         aead_key_material(key, &K);
@@ -2308,11 +2063,11 @@ rcdc_status aead_launch(rcdc_ctx *ctx, bool open, const uint8_t key[64], std::ve
         nb += B.blobs.size();
         nu += B.units.size();
     }
-    if ((rs = ensure_dev(&ctx->d_aead_blobs, &ctx->cap_aead_blobs, nb))) return rs;
-    if ((rs = ensure_dev(&ctx->d_aead_units, &ctx->cap_aead_units, nu))) return rs;
-    if ((rs = ensure_dev(&ctx->d_aead_unit0, &ctx->cap_aead_unit0, nb + bt.size()))) return rs;
-    if ((rs = ensure_dev(&ctx->d_aead_partials, &ctx->cap_aead_partials, nu * 5))) return rs;
-    if ((rs = ensure_dev(&ctx->d_aead_status, &ctx->cap_aead_status, nb))) return rs;
+    if ((rs = ctx->d_aead_blobs.ensure(nb))) return rs;
+    if ((rs = ctx->d_aead_units.ensure(nu))) return rs;
+    if ((rs = ctx->d_aead_unit0.ensure(nb + bt.size()))) return rs;
+    if ((rs = ctx->d_aead_partials.ensure(nu * 5))) return rs;
+    if ((rs = ctx->d_aead_status.ensure(nb))) return rs;
     // the call's uploads go async on st from one page-locked buffer (free
     // again: the last call's work is done, aead_done above).  Synchronous
     // copies from pageable memory queued behind other streams' multi-GiB
@@ -2340,7 +2095,7 @@ rcdc_status aead_launch(rcdc_ctx *ctx, bool open, const uint8_t key[64], std::ve
         return e;
     };
     if (staging && !staging->empty()) {
-        if ((rs = ensure_dev(&ctx->d_aead_stage, &ctx->cap_aead_stage, staging->size() + 16)))
+        if ((rs = ctx->d_aead_stage.ensure(staging->size() + 16)))
             return rs;
         HIP_TRY(upload(ctx->d_aead_stage, staging->data(), staging->size()));
     }
@@ -2436,7 +2191,7 @@ rcdc_status copy_units_run(rcdc_ctx *ctx, const std::vector<uint64_t> &copies, v
     std::lock_guard<std::mutex> lk(ctx->aead_mu);
     const uint64_t nu = copies.size() / 4;
     rcdc_status rs;
-    if ((rs = ensure_dev(&ctx->d_copy_units, &ctx->cap_copy_units, copies.size()))) return rs;
+    if ((rs = ctx->d_copy_units.ensure(copies.size()))) return rs;
     HIP_TRY(hipMemcpyAsync(ctx->d_copy_units, copies.data(), copies.size() * 8,
                            hipMemcpyHostToDevice, st));
     HIP_TRY(launch_copy_ranges((uint8_t *)d_out, ctx->d_copy_units, (uint32_t)nu,
@@ -2699,25 +2454,25 @@ rcdc_status zstd_compress(rcdc_ctx *ctx, int level, const void *d_in, const rcdc
     rcdc_status rs;
     if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
     if (!ctx->d_zstd_tabs) {
-        if ((rs = ensure_dev(&ctx->d_zstd_tabs, &ctx->cap_zstd_tabs, 1))) return rs;
+        if ((rs = ctx->d_zstd_tabs.ensure(1))) return rs;
         HIP_TRY(hipMemcpy(ctx->d_zstd_tabs, &zstd_tables(), sizeof(ZstdTables),
                           hipMemcpyHostToDevice));
     }
     const uint32_t grid = zstd_block_grid((uint32_t)std::max(ctx->num_cus, 1), level);
     // (+ 8 words: the last wave's 16-byte literal loads may pass its region by 20 bytes)
-    if ((rs = ensure_dev(&ctx->d_zstd_seq, &ctx->cap_zstd_seq, (uint64_t)grid * kZstdMaxSeq + 8)))
+    if ((rs = ctx->d_zstd_seq.ensure((uint64_t)grid * kZstdMaxSeq + 8)))
         return rs;
     const uint64_t nbl = blks.size(), nbo = blobs.size();
-    if ((rs = ensure_dev(&ctx->d_zstd_blobs, &ctx->cap_zstd_blobs, nbo))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zstd_blks, &ctx->cap_zstd_blks, nbl))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zstd_res, &ctx->cap_zstd_res, nbl))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zstd_bpos, &ctx->cap_zstd_bpos, nbl))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zstd_lens, &ctx->cap_zstd_lens, nbo))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zstd_slots, &ctx->cap_zstd_slots, maxw * kZstdSlot))) return rs;
+    if ((rs = ctx->d_zstd_blobs.ensure(nbo))) return rs;
+    if ((rs = ctx->d_zstd_blks.ensure(nbl))) return rs;
+    if ((rs = ctx->d_zstd_res.ensure(nbl))) return rs;
+    if ((rs = ctx->d_zstd_bpos.ensure(nbl))) return rs;
+    if ((rs = ctx->d_zstd_lens.ensure(nbo))) return rs;
+    if ((rs = ctx->d_zstd_slots.ensure(maxw * kZstdSlot))) return rs;
     const uint64_t farw = zstd_far_words(level, maxw);
-    if (farw && (rs = ensure_dev(&ctx->d_zstd_far, &ctx->cap_zstd_far, farw))) return rs;
+    if (farw && (rs = ctx->d_zstd_far.ensure(farw))) return rs;
     // the block kernel's queue: 8 counters 64 B apart per window
-    if ((rs = ensure_dev(&ctx->d_zstd_queue, &ctx->cap_zstd_queue, wins.size() * 128))) return rs;
+    if ((rs = ctx->d_zstd_queue.ensure(wins.size() * 128))) return rs;
     HIP_TRY(hipMemsetAsync(ctx->d_zstd_queue, 0, wins.size() * 128 * 4, st));
     HIP_TRY(hipMemcpyAsync(ctx->d_zstd_blobs, blobs.data(), nbo * sizeof(ZstdBlob),
                            hipMemcpyHostToDevice, st));
@@ -2728,15 +2483,15 @@ rcdc_status zstd_compress(rcdc_ctx *ctx, int level, const void *d_in, const rcdc
             fprintf(stderr, "rcdc zstd buf %-6s [%p, %p) %llu B\n", nm, p, (const void *)((const char *)p + bytes),
                     (unsigned long long)bytes);
         };
-        rng("seq", ctx->d_zstd_seq, ctx->cap_zstd_seq * 8);
-        rng("slots", ctx->d_zstd_slots, ctx->cap_zstd_slots);
-        rng("far", ctx->d_zstd_far, ctx->cap_zstd_far * 4);
-        rng("res", ctx->d_zstd_res, ctx->cap_zstd_res * 8);
-        rng("bpos", ctx->d_zstd_bpos, ctx->cap_zstd_bpos * 8);
-        rng("blobs", ctx->d_zstd_blobs, ctx->cap_zstd_blobs * sizeof(ZstdBlob));
-        rng("blks", ctx->d_zstd_blks, ctx->cap_zstd_blks * sizeof(ZstdBlk));
-        rng("tabs", ctx->d_zstd_tabs, ctx->cap_zstd_tabs * sizeof(ZstdTables));
-        rng("queue", ctx->d_zstd_queue, ctx->cap_zstd_queue * 4);
+        rng("seq", ctx->d_zstd_seq, ctx->d_zstd_seq.capacity() * 8);
+        rng("slots", ctx->d_zstd_slots, ctx->d_zstd_slots.capacity());
+        rng("far", ctx->d_zstd_far, ctx->d_zstd_far.capacity() * 4);
+        rng("res", ctx->d_zstd_res, ctx->d_zstd_res.capacity() * 8);
+        rng("bpos", ctx->d_zstd_bpos, ctx->d_zstd_bpos.capacity() * 8);
+        rng("blobs", ctx->d_zstd_blobs, ctx->d_zstd_blobs.capacity() * sizeof(ZstdBlob));
+        rng("blks", ctx->d_zstd_blks, ctx->d_zstd_blks.capacity() * sizeof(ZstdBlk));
+        rng("tabs", ctx->d_zstd_tabs, ctx->d_zstd_tabs.capacity() * sizeof(ZstdTables));
+        rng("queue", ctx->d_zstd_queue, ctx->d_zstd_queue.capacity() * 4);
         rng("in", d_in, 0);
         rng("out", d_out, 0);
         fprintf(stderr, "rcdc zstd grid %u nblk %llu maxw %llu level %d\n", grid, (unsigned long long)nbl,
@@ -2846,10 +2601,10 @@ rcdc_status zstd_check(rcdc_ctx *ctx, const void *d_frames, const void *d_data,
     if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
     // resident waves per CU (12 or 16, by the registers' budget)
     const uint32_t grid = (uint32_t)std::max(ctx->num_cus, 1) * zstd_check_waves_per_cu();
-    if ((rs = ensure_dev(&ctx->d_zck_refs, &ctx->cap_zck_refs, 4ull * n))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zck_order, &ctx->cap_zck_order, (uint64_t)n + 16))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zck_status, &ctx->cap_zck_status, n))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zck_scratch, &ctx->cap_zck_scratch, zstd_check_scratch_bytes(grid))))
+    if ((rs = ctx->d_zck_refs.ensure(4ull * n))) return rs;
+    if ((rs = ctx->d_zck_order.ensure((uint64_t)n + 16))) return rs;
+    if ((rs = ctx->d_zck_status.ensure(n))) return rs;
+    if ((rs = ctx->d_zck_scratch.ensure(zstd_check_scratch_bytes(grid))))
         return rs;
     uint32_t *ctr = ctx->d_zck_order + n;  // the queue counter sits after the order array
     HIP_TRY(hipMemcpyAsync(ctx->d_zck_refs, refs, sizeof(rcdc_zstd_check_ref) * n,
@@ -2860,8 +2615,8 @@ rcdc_status zstd_check(rcdc_ctx *ctx, const void *d_frames, const void *d_data,
         for (uint32_t i = 0; i < n; i++)
             blk0[i + 1] = blk0[i] + std::max<uint64_t>((refs[i].data_len + kZstdBlock - 1) / kZstdBlock, 1);
         const uint64_t nblk = blk0[n];
-        if ((rs = ensure_dev(&ctx->d_zck_blk0, &ctx->cap_zck_blk0, n + 1ull))) return rs;
-        if ((rs = ensure_dev(&ctx->d_zck_blks, &ctx->cap_zck_blks, nblk * zstd_blkdesc_bytes())))
+        if ((rs = ctx->d_zck_blk0.ensure(n + 1ull))) return rs;
+        if ((rs = ctx->d_zck_blks.ensure(nblk * zstd_blkdesc_bytes())))
             return rs;
         HIP_TRY(hipMemcpyAsync(ctx->d_zck_blk0, blk0.data(), 8ull * (n + 1), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(ctr, 0, 4, st));
@@ -2932,12 +2687,12 @@ rcdc_status zstd_decompress(rcdc_ctx *ctx, const void *d_frames, const rcdc_zstd
     rcdc_status rs;
     if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
     const uint32_t grid = (uint32_t)std::max(ctx->num_cus, 1) * zdx_waves_per_cu();
-    if ((rs = ensure_dev(&ctx->d_zdx_refs, &ctx->cap_zdx_refs, 4ull * n))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zdx_lens, &ctx->cap_zdx_lens, n))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zdx_frm, &ctx->cap_zdx_frm, n))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zdx_place, &ctx->cap_zdx_place, n))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zdx_order, &ctx->cap_zdx_order, 2ull * n + 16))) return rs;
-    if ((rs = ensure_dev(&ctx->d_zdx_status, &ctx->cap_zdx_status, n))) return rs;
+    if ((rs = ctx->d_zdx_refs.ensure(4ull * n))) return rs;
+    if ((rs = ctx->d_zdx_lens.ensure(n))) return rs;
+    if ((rs = ctx->d_zdx_frm.ensure(n))) return rs;
+    if ((rs = ctx->d_zdx_place.ensure(n))) return rs;
+    if ((rs = ctx->d_zdx_order.ensure(2ull * n + 16))) return rs;
+    if ((rs = ctx->d_zdx_status.ensure(n))) return rs;
     const uint8_t *frames = (const uint8_t *)d_frames;
     HIP_TRY(hipMemcpyAsync(ctx->d_zdx_refs, refs, sizeof(rcdc_zstd_dec_ref) * n, hipMemcpyHostToDevice, st));
     // 1. count: blocks and workspace bytes per frame
@@ -2971,7 +2726,7 @@ rcdc_status zstd_decompress(rcdc_ctx *ctx, const void *d_frames, const rcdc_zstd
         groups.push_back(G);
         i = G.b;
     }
-    if ((rs = ensure_dev(&ctx->d_zdx_ws, &ctx->cap_zdx_ws, peak))) return rs;
+    if ((rs = ctx->d_zdx_ws.ensure(peak))) return rs;
     HIP_TRY(hipMemcpyAsync(ctx->d_zdx_place, place.data(), sizeof(ZdxPlace) * n, hipMemcpyHostToDevice, st));
     uint32_t *d_list = ctx->d_zdx_order, *d_ord = ctx->d_zdx_order + n, *ctr = ctx->d_zdx_order + 2ull * n;
     std::vector<uint32_t> list, order;
@@ -3266,15 +3021,14 @@ rcdc_status rcdc_place_blobs(rcdc_ctx *ctx, const void *const *d_ins, const uint
     hipStream_t st;
     rcdc_status rs;
     if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
-    if ((rs = ensure_dev(&ctx->d_place_tiles, &ctx->cap_place_tiles, R))) return rs;
-    if ((rs = ensure_dev(&ctx->d_place_dests, &ctx->cap_place_dests,
-                         std::max<uint64_t>(ndests_total, 1))))
+    if ((rs = ctx->d_place_tiles.ensure(R))) return rs;
+    if ((rs = ctx->d_place_dests.ensure(std::max<uint64_t>(ndests_total, 1))))
         return rs;
     if (ndests_total)
         HIP_TRY(hipMemcpyAsync(ctx->d_place_dests, daddr, (size_t)ndests_total * 8,
                                hipMemcpyHostToDevice, st));
     if (want_zero) {
-        if ((rs = ensure_dev(&ctx->d_place_nz, &ctx->cap_place_nz, nblobs))) return rs;
+        if ((rs = ctx->d_place_nz.ensure(nblobs))) return rs;
         HIP_TRY(hipMemsetAsync(ctx->d_place_nz, 0, (size_t)nblobs * 4, st));
     }
     if (!ctx->place_up) HIP_TRY(hipStreamCreateWithFlags(&ctx->place_up, hipStreamNonBlocking));

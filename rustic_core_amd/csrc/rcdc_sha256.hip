@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "rcdc_internal.h"
+#include "rcdc_launch.h"
 
 namespace rcdc {
 

@@ -40,6 +40,7 @@
 #include <cstdlib>
 
 #include "rcdc_internal.h"
+#include "rcdc_launch.h"
 
 using namespace rcdc;
 

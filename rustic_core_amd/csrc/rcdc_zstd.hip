@@ -42,6 +42,7 @@
 #include <cstring>
 
 #include "rcdc_internal.h"
+#include "rcdc_launch.h"
 
 using namespace rcdc;
 

@@ -34,6 +34,7 @@
 #include <cstring>
 
 #include "rcdc_internal.h"
+#include "rcdc_launch.h"
 #include "rcdc_zstd_bits.h"
 
 using namespace rcdc;

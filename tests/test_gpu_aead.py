@@ -123,6 +123,25 @@ def test_seal_counter_carry(gpu_ctx, oracle_mod, rng):
         assert g == oracle_mod.seal(key._key, nc, d)
 
 
+def test_seal_regrowth(gpu_ctx, oracle_mod):
+    """The context's descriptor arrays grow and are used again at the old
+    size: 8 blobs, then 1500 (1500 x 48 B of blob descriptors pass the 64 KiB
+    floor of a device array, so the blob and unit-offset arrays are
+    reallocated), then the first 8 again, all with one key on one context."""
+    from rustic_core_amd.crypto import Key
+    rng = np.random.default_rng(0x9E0)  # its own: the module's stream stays as it was
+    key = Key(_rand(rng, 64))
+    first = [_rand(rng, n) for n in [0, 1, 16, 200, 4096, 65537, 3 * 65536 + 7, 100_000]]
+    many = [_rand(rng, int(n)) for n in rng.integers(0, 201, 1500)]
+    assert len(many) * 48 > 65536
+    for datas in (first, many, first):
+        nonces = [_rand(rng, 16) for _ in datas]
+        got, *_ = _seal_dev(key, datas, nonces)
+        assert len(got) == len(datas)
+        for i, (d, nc, g) in enumerate(zip(datas, nonces, got)):
+            assert g == oracle_mod.seal(key._key, nc, d), (len(datas), i)
+
+
 def test_seal_max_chunk_and_many(gpu_ctx, oracle_mod, rng):
     """A max-size chunk (8 MiB, rabin.rs:12) and 200 chunk-like blobs."""
     from rustic_core_amd.crypto import Key

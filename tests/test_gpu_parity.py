@@ -118,6 +118,27 @@ def test_batch_host_api(gpu_ctx):
         assert np.array_equal(got[i], oracle.chunk_cuts(b)), i
 
 
+def test_batch_host_api_regrowth(gpu_ctx):
+    """A lane's cached plan is rebuilt into larger arrays and then into the
+    old shape again: 8 buffers, then 1100 (1100 x 64 B of stream descriptors
+    pass the 64 KiB floor of a device array, so the array is reallocated on
+    the lane's upload stream), then the 8 again.  The calls come from one
+    thread, which takes the lane it released last, so all three use one lane
+    and one plan.  The 4 KiB buffers are below min: one cut each."""
+    small = [oracle.stdrng_bytes(7 + i, n) for i, n in
+             enumerate([0, 1, 63, 4096, 512 * KiB, 512 * KiB + 64, 512 * KiB + 65, 3 * MiB + 7])]
+    block = np.random.default_rng(0x1100).integers(0, 256, (1100, 4 * KiB), dtype=np.uint8)
+    many = [block[i] for i in range(len(block))]
+    assert len(many) * 64 > 65536
+    want_small = [oracle.chunk_cuts(b) for b in small]
+    for bufs, want in [(small, want_small), (many, [oracle.chunk_cuts(b) for b in many]),
+                       (small, want_small)]:
+        got = gpu_ctx.chunk_batch(bufs)
+        assert len(got) == len(bufs)
+        for i in range(len(bufs)):
+            assert np.array_equal(got[i], want[i]), (len(bufs), i)
+
+
 # ---------------------------------------------------------------- edge sizes
 @pytest.mark.parametrize("n", [0, 1, 64, 4095, 512 * KiB - 1, 512 * KiB, 512 * KiB + 1,
                                512 * KiB + 63, 512 * KiB + 64, 512 * KiB + 65,
