@@ -63,14 +63,14 @@
 
 #include "../../include/rcdc.h"
 #include "rcdc_host.h"
+#include "rcdc_ingest_steps.h"
 #include "rcdc_launch.h"
 
 using namespace rcdc;
+using steps::PackSizer;
 
 namespace {
 
-constexpr uint64_t kMaxPackSize = 4076ull << 20;  // packer.rs:58
-constexpr uint32_t kMaxPackCount = 10000;         // packer.rs:60
 constexpr uint32_t kSrcStaging = 0, kSrcCarry = 1;
 
 uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
@@ -100,14 +100,57 @@ struct Id32Hash {
     }
 };
 
-// PackSizer (packer.rs:65-200): only pack_size() steers should_save.
-struct PackSizer {
-    uint64_t default_size, grow, limit, current;
-    uint64_t pack_size() const {
-        uint64_t size = default_size;
-        if (grow) size = ((uint64_t)std::sqrt((double)current) * grow + default_size) & 0xFFFFFFFFull;
-        return std::min(std::min(size, limit), kMaxPackSize);
+// ---- owners: whoever holds one frees it, with the engine's device current --
+// A HIP event or stream, move-only.
+template <typename H, hipError_t (*Destroy)(H)>
+struct HipOwner {
+    H h = nullptr;
+    HipOwner() = default;
+    HipOwner(HipOwner &&o) noexcept : h(o.h) { o.h = nullptr; }
+    ~HipOwner() { reset(); }
+    void reset() {
+        if (h) (void)Destroy(h);
+        h = nullptr;
     }
+    operator H() const { return h; }
+};
+using Stream = HipOwner<hipStream_t, hipStreamDestroy>;
+struct Event : HipOwner<hipEvent_t, hipEventDestroy> {
+    hipError_t create() { return hipEventCreateWithFlags(&h, hipEventDisableTiming); }
+};
+
+// The engine's allocations: counted (rcdc_ingest_mem_live) and, in create,
+// failable on demand (RCDC_INGEST_FAIL_ALLOC).
+hipError_t ing_alloc(rcdc_ingest *g, void **p, uint64_t n, bool pinned);
+hipError_t ing_free(void *p);
+
+// One buffer of the engine: device memory or page-locked host memory,
+// `cap` elements, freed by its holder's destructor.
+template <typename T>
+struct IngBuf {
+    T *p = nullptr;
+    uint64_t cap = 0;
+    bool pinned = false;
+    IngBuf() = default;
+    IngBuf(const IngBuf &) = delete;
+    ~IngBuf() { (void)release(); }
+    operator T *() const { return p; }
+    hipError_t release() {
+        T *q = p;
+        p = nullptr, cap = 0;
+        return q ? ing_free(q) : hipSuccess;
+    }
+    // exactly n elements (create)
+    hipError_t alloc(rcdc_ingest *g, uint64_t n, bool pin) {
+        pinned = pin;
+        const hipError_t e = ing_alloc(g, (void **)&p, n * sizeof(T), pin);
+        cap = e == hipSuccess ? n : 0;
+        return e;
+    }
+    // At least `need` elements; when that takes a new allocation, one of
+    // `grown` elements -- each site's own headroom rule -- and the contents
+    // are lost.  False: the engine's error is set.
+    bool ensure(rcdc_ingest *g, uint64_t need, uint64_t grown, const char *what);
 };
 
 // One stream (rcdc_ingest_stream_open .. close): its carry between batches
@@ -157,18 +200,40 @@ struct Unit {
 enum SlotState { kFree = 0, kOpen, kClosed, kSubmitted };
 
 struct InSlot {
-    uint8_t *host = nullptr;
-    uint64_t cap = 0, used = 0;
+    IngBuf<uint8_t> host;  // page-locked, batch_cap bytes
+    uint64_t used = 0;
     uint32_t open_res = 0;
     SlotState state = kFree;
     std::vector<FileEnt> files;
-    hipEvent_t h2d = nullptr;
+    Event h2d;
     bool h2d_pending = false;
     std::atomic<int> host_jobs{0};  // long-id jobs still reading this slot
     std::atomic<bool> h2d_issued{false};  // its last H2D piece and h2d are enqueued
     uint64_t close_seq = 0;
     bool has_stream = false;        // holds stream pieces: enters the pipeline in close order
     double t_first = 0;             // its first reservation (slot_max_age_ms)
+    void reset(SlotState to) {      // empty again: free, or open for new reservations
+        state = to;
+        used = 0;
+        files.clear();
+        has_stream = false;
+        t_first = 0;
+    }
+};
+
+struct OutSlot {
+    IngBuf<uint8_t> host;  // page-locked
+    std::atomic<int> packs_left{0};
+    bool busy = false;
+};
+
+// The end of one D2H group: `fin` is recorded after its last piece, `issued`
+// set once ev_out and fin are enqueued.  Shared by the copy job (the pump
+// records), the wait item (the waiter syncs) and the engine's last_d2h (the
+// next pack build waits for `issued`): the last of them frees the event.
+struct D2HDone {
+    Event fin;
+    std::atomic<bool> issued{false};
 };
 
 // A batch between stage A and stage B.
@@ -186,34 +251,36 @@ struct Batch {
     std::vector<uint8_t> ids;            // 32 B per chunk
     std::vector<uint32_t> short_idx;     // chunks whose ids the device computes
     std::vector<uint64_t> seal_off, seal_len, ulen;
-    hipEvent_t ids_ev = nullptr;
     std::atomic<int> long_jobs{0};
-    bool finalize = false;
+    // stage B: the open pack's blobs then this batch's new ones; the packs
+    // closed (blobs [0, open_from)), laid out back to back in `total` bytes;
+    // each blob's offset in its pack; the output slot and the D2H groups
+    std::vector<rcdc_pack_blob> blobs;
+    std::vector<std::pair<uint32_t, uint32_t>> grp;
+    size_t open_from = 0;
+    std::vector<rcdc_pack> packs;
+    uint64_t total = 0;
+    std::vector<uint32_t> boffs;
+    OutSlot *out = nullptr;
+    std::vector<std::pair<steps::D2HRange, std::shared_ptr<D2HDone>>> d2h;
 };
 
 // Device buffers of one pipeline slot.
-struct PSlot {
-    rcdc_plan *plan = nullptr;
-    uint8_t *arena = nullptr;
-    uint64_t arena_cap = 0;
-    uint8_t *staging = nullptr;  // sealed blobs
-    uint64_t staging_cap = 0;
-    uint64_t *d_refs = nullptr;  // (off, len) of the short chunks
-    uint64_t refs_cap = 0;       // chunks
-    uint64_t *h_refs = nullptr;  // page-locked upload source
-    uint8_t *d_dig = nullptr;
-    hipStream_t s_ids = nullptr;
-    hipEvent_t ev_ids = nullptr;
-    hipEvent_t ev_sealed = nullptr;   // stage A's device work done (s_comp)
-    hipEvent_t ev_retired = nullptr;  // stage B done with the staging area (s_back)
-    bool busy = false;                // a batch holds this slot (submit .. stage B)
+struct PlanDel {
+    void operator()(rcdc_plan *p) const { rcdc_plan_destroy(p); }
 };
-
-struct OutSlot {
-    uint8_t *host = nullptr;
-    uint64_t cap = 0;
-    std::atomic<int> packs_left{0};
-    bool busy = false;
+struct PSlot {
+    std::unique_ptr<rcdc_plan, PlanDel> plan;
+    IngBuf<uint8_t> arena;
+    IngBuf<uint8_t> staging;   // sealed blobs
+    IngBuf<uint64_t> d_refs;   // (off, len) of the short chunks: 2 per chunk
+    IngBuf<uint64_t> h_refs;   // page-locked upload source
+    IngBuf<uint8_t> d_dig;     // 32 B per chunk
+    Stream s_ids;
+    Event ev_ids;
+    Event ev_sealed;   // stage A's device work done (s_comp)
+    Event ev_retired;  // stage B done with the staging area (s_back)
+    bool busy = false;  // a batch holds this slot (submit .. stage B)
 };
 
 struct PackJob {
@@ -222,6 +289,34 @@ struct PackJob {
     uint32_t header_len = 0;
     std::vector<rcdc_ingest_blob> blobs;
     uint8_t id[32];
+};
+
+// The engine's environment knobs, read by each rcdc_ingest_create.
+long long env_num(const char *name, long long dflt) {
+    const char *e = getenv(name);
+    return e ? strtoll(e, nullptr, 10) : dflt;
+}
+struct Knobs {
+    // the last batches whose chunks above 1 MiB the host hashes too
+    size_t tail_batches = (size_t)env_num("RCDC_INGEST_TAIL_BATCHES", 2);
+    // bytes of packs per D2H group
+    uint64_t d2h_group = (uint64_t)env_num("RCDC_INGEST_D2H_GROUP", 256ll << 20);
+    // 0: the last batches' packs go back in such groups too, not one by one
+    bool tail_single = env_num("RCDC_INGEST_TAIL_SINGLE", 1) != 0;
+    // pool threads that never take a pack-id job
+    uint32_t id_threads = (uint32_t)env_num("RCDC_INGEST_ID_THREADS", 0);
+    // 0: wait for events in hipEventSynchronize, not by polling
+    bool poll = env_num("RCDC_INGEST_POLL", 1) != 0;
+    // batch copies by a shader kernel on this many workgroups (0: the DMA engines)
+    uint32_t kcopy = (uint32_t)std::max(env_num("RCDC_INGEST_KCOPY", 0), 0ll);
+    // bytes per H2D / D2H copy, at least 1 MiB
+    uint64_t copy_piece = (uint64_t)std::max(env_num("RCDC_INGEST_COPY_PIECE", 64ll << 20), 1ll << 20);
+    // 1: the per-batch timeline on stderr at finish; 2: with the chunking's own ends
+    int prof = getenv("RCDC_INGEST_PROF") ? (int)std::max(env_num("RCDC_INGEST_PROF", 0), 1ll) : 0;
+    // k: create's k-th allocation fails (tests)
+    uint32_t fail_alloc = (uint32_t)std::max(env_num("RCDC_INGEST_FAIL_ALLOC", 0), 0ll);
+    // a line on stderr per regrowth
+    bool alloc_log = getenv("RCDC_ALLOC_LOG") != nullptr;
 };
 
 }  // namespace
@@ -261,8 +356,7 @@ struct rcdc_ingest {
     int level = 0;
     bool compress = true, verify = true;
     uint64_t batch_cap = 0, long_chunk = 0;
-    uint64_t copy_piece = 64ull << 20;  // bytes per H2D / D2H copy (RCDC_INGEST_COPY_PIECE)
-    uint32_t kcopy = 0;  // RCDC_INGEST_KCOPY: batch copies by a shader kernel on this many workgroups
+    Knobs knobs;
     uint32_t depth = 4, nin = 4, nout = 4, nthreads = 8;
     PackSizer sizer{};
     // input slots
@@ -273,29 +367,26 @@ struct rcdc_ingest {
     std::deque<InSlot *> ready;         // closed, all commits in: stage A order
     // device pipeline
     std::vector<PSlot> ps;
-    uint8_t *frames = nullptr;  // zstd frames, then the verify's opened frames
-    uint64_t frames_cap = 0;
-    uint8_t *d_packs = nullptr;
-    uint64_t d_packs_cap = 0;
-    uint8_t *carry[2] = {nullptr, nullptr};
-    uint64_t carry_cap[2] = {0, 0};
+    IngBuf<uint8_t> frames;  // zstd frames, then the verify's opened frames
+    IngBuf<uint8_t> d_packs;
+    IngBuf<uint8_t> carry[2];
     int carry_cur = 0;
     std::vector<rcdc_pack_blob> carry_blobs;  // the open pack's blobs (src = kSrcCarry)
-    hipStream_t s_in = nullptr, s_comp = nullptr, s_out = nullptr;
-    hipEvent_t ev_comp = nullptr, ev_out = nullptr, ev_back = nullptr;  // (front / back / out)
+    Stream s_in, s_comp, s_out;
+    Event ev_comp, ev_out, ev_back;  // (front / back / out)
     std::vector<std::unique_ptr<OutSlot>> outs;
     std::deque<std::unique_ptr<Batch>> submitted;  // H2D issued, stage A next (front thread)
     std::deque<std::unique_ptr<Batch>> inflight;   // stage A done, stage B next (back thread)
     bool front_done = false;                       // every batch has been through stage A
     uint64_t nclosed = 0;                          // input slots closed so far
-    hipStream_t s_back = nullptr;                  // stage B's device work
+    Stream s_back;                                 // stage B's device work
     uint64_t nbatches = 0, next_seq = 0;
     rcdc_index *idx = nullptr;  // the index's ids + the packer's (own, or shared)
-    bool own_idx = true;
+    std::unique_ptr<rcdc_index> own_idx;
     // streams
     uint64_t max_chunk = 0;          // ctx max: a carry's bound
     uint64_t asm_base = 0, asm_cap = 0;  // the arena's assembly region
-    uint8_t *carry_pool = nullptr;   // max_streams device carry slots of max_chunk bytes
+    IngBuf<uint8_t> carry_pool;      // max_streams device carry slots of max_chunk bytes
     std::vector<int> free_cslots;
     std::unordered_map<uint64_t, std::shared_ptr<StreamSt>> streams;  // open handles
     uint64_t next_stream = 1;
@@ -303,32 +394,24 @@ struct rcdc_ingest {
     std::deque<InSlot *> closed_q;   // closed slots not yet ready, in close order
     double pack_t0 = 0;              // the open pack's first blob (MAX_AGE)
     double pack_max_age = 300, slot_max_age = 1;
-    // allocations of this engine (rcdc_ingest_mem_live); RCDC_INGEST_FAIL_ALLOC
-    // = k fails the k-th allocation of create (tests)
-    uint32_t nalloc = 0, fail_alloc = 0;
+    uint32_t nalloc = 0;  // allocations so far (knobs.fail_alloc)
     // threads
     std::thread worker, back, waiter, feeder;
-    // the feeder's copy pump: batches waiting for their H2D pieces
-    struct H2DJob {
+    // the feeder's copy pump: batches waiting for their H2D pieces, and the
+    // pack bytes' D2H groups, queued by stage B (back thread).  Whoever drops
+    // a job frees its events.
+    struct CopyJob {
         uint8_t *dst;
         const uint8_t *src;
         uint64_t len, done;
-        InSlot *in;
+        InSlot *in;                    // H2D: its h2d event ends the copy
+        Event after;                   // D2H: the pack build (s_back); the first piece waits on it
+        std::shared_ptr<D2HDone> fin;  // D2H
     };
-    std::deque<H2DJob> h2d_q;
-    // ... and the pack bytes' D2H, queued by stage B (back thread)
-    struct D2HJob {
-        uint8_t *dst;
-        const uint8_t *src;
-        uint64_t len, done;
-        hipEvent_t after;  // the pack build (s_back); the first piece waits on it
-        hipEvent_t fin;    // recorded after the last piece (the waiter syncs on it)
-        std::shared_ptr<std::atomic<bool>> issued;  // ev_out and fin are enqueued
-        bool waited;
-    };
+    std::deque<CopyJob> h2d_q;
     std::mutex d2h_mu;
-    std::deque<D2HJob> d2h_q;
-    std::shared_ptr<std::atomic<bool>> last_d2h;  // the last D2H job's `issued`
+    std::deque<CopyJob> d2h_q;
+    std::shared_ptr<D2HDone> last_d2h;  // the last D2H group queued
     int submitting = 0;  // slots taken from `ready` whose batch is not in `submitted` yet
     std::vector<std::thread> pool;
     std::mutex pool_mu;
@@ -339,8 +422,7 @@ struct rcdc_ingest {
     std::mutex wait_mu;
     std::condition_variable wait_cv;
     struct WaitItem {
-        hipEvent_t ev;
-        std::shared_ptr<std::atomic<bool>> issued;
+        std::shared_ptr<D2HDone> done;
         uint64_t batch;
         std::vector<std::shared_ptr<PackJob>> jobs;
     };
@@ -354,9 +436,8 @@ struct rcdc_ingest {
     std::string err_msg;
     rcdc_ingest_stats st{};
     double t_first = 0;
-    // RCDC_INGEST_PROF=1: per batch (stage A start, sync points, end; stage B
-    // start, ids wait end, end), printed by rcdc_ingest_finish
-    int prof = 0;
+    // knobs.prof: per batch (stage A start, sync points, end; stage B start,
+    // ids wait end, end), printed by rcdc_ingest_finish
     std::vector<std::vector<double>> tl;
     std::vector<double> tl_d2h, tl_ids;  // per batch: packs landed, last pack id
 };
@@ -392,15 +473,14 @@ void set_err(Ing *g, rcdc_status s, const std::string &m) {
         }                                                                                 \
     } while (0)
 
-// ---- the engine's allocations: counted (rcdc_ingest_mem_live), freed on
-// every path (free_all), and failable on demand (RCDC_INGEST_FAIL_ALLOC)
+// ---- the engine's allocations (IngBuf), counted for rcdc_ingest_mem_live
 std::mutex g_alloc_mu;
 std::unordered_map<void *, std::pair<uint64_t, bool>> g_allocs;  // ptr -> (bytes, pinned)
 uint64_t g_live_pinned = 0, g_live_dev = 0;
 
 hipError_t ing_alloc(Ing *g, void **p, uint64_t n, bool pinned) {
     *p = nullptr;
-    if (g && g->fail_alloc && ++g->nalloc == g->fail_alloc) return hipErrorOutOfMemory;
+    if (g && g->knobs.fail_alloc && ++g->nalloc == g->knobs.fail_alloc) return hipErrorOutOfMemory;
     const hipError_t e = pinned ? hipHostMalloc(p, n, hipHostMallocDefault) : hipMalloc(p, n);
     if (e != hipSuccess) {
         *p = nullptr;
@@ -412,17 +492,7 @@ hipError_t ing_alloc(Ing *g, void **p, uint64_t n, bool pinned) {
     return hipSuccess;
 }
 
-template <typename T>
-hipError_t ing_alloc(Ing *g, T **p, uint64_t n, bool pinned) {
-    return ing_alloc(g, (void **)p, n, pinned);
-}
-
-// Frees and nulls *p (no-op on null).
-template <typename T>
-hipError_t ing_free(T **p) {
-    if (!*p) return hipSuccess;
-    void *q = (void *)*p;
-    *p = nullptr;
+hipError_t ing_free(void *q) {
     bool pinned = false;
     {
         std::lock_guard<std::mutex> lk(g_alloc_mu);
@@ -437,24 +507,22 @@ hipError_t ing_free(T **p) {
 }
 
 template <typename T>
-bool ensure_dev(Ing *g, T **p, uint64_t *cap, uint64_t need) {
-    if (*p && *cap >= need) return true;
-    static const bool log = getenv("RCDC_ALLOC_LOG") != nullptr;
-    if (log && *p)
-        fprintf(stderr, "rcdc ingest: regrow %llu -> %llu x %zu B (hipFree: device sync)\n",
-                (unsigned long long)*cap, (unsigned long long)need, sizeof(T));
-    ING_HIP(g, ing_free(p));
-    *cap = 0;
-    const uint64_t n = need + need / 8 + 1;
-    ING_HIP(g, ing_alloc(g, p, n * sizeof(T), false));
-    *cap = n;
+bool IngBuf<T>::ensure(Ing *g, uint64_t need, uint64_t grown, const char *what) {
+    if (p && cap >= need) return true;
+    if (g->knobs.alloc_log && p)
+        fprintf(stderr, "rcdc ingest: regrow %s %llu -> %llu x %zu B (hipFree: device sync)\n", what,
+                (unsigned long long)cap, (unsigned long long)need, sizeof(T));
+    ING_HIP(g, release());
+    ING_HIP(g, alloc(g, grown, pinned));
     return true;
 }
+// the device buffers' headroom: an eighth
+uint64_t grow8(uint64_t need) { return need + need / 8 + 1; }
 
 // Host SHA-256 jobs; `urgent` ones (the long chunks' ids, which gate a
 // batch's stage B) go before the pack ids, in the order posted (longest
 // first).  Pack-id jobs hold a thread for tens of ms (4 packs of ~40 MB), so
-// RCDC_INGEST_ID_THREADS (default 2) threads never take one: a long-id job
+// knobs.id_threads threads never take one: a long-id job
 // then starts at once instead of after the running pack jobs (r5z2: the last
 // batches' stage B waited ~14 ms for a free thread).
 void post(Ing *g, std::function<void()> fn, bool urgent = false) {
@@ -467,8 +535,7 @@ void post(Ing *g, std::function<void()> fn, bool urgent = false) {
 }
 
 void pool_main(Ing *g) {
-    static const uint32_t reserve =
-        getenv("RCDC_INGEST_ID_THREADS") ? (uint32_t)atoi(getenv("RCDC_INGEST_ID_THREADS")) : 0u;
+    const uint32_t reserve = g->knobs.id_threads;
     const uint32_t pack_cap = g->nthreads > reserve ? g->nthreads - reserve : 1u;
     for (;;) {
         std::function<void()> fn;
@@ -502,13 +569,12 @@ void pool_main(Ing *g) {
     }
 }
 
-// Wait for an event by polling (RCDC_INGEST_POLL, default on) instead of
+// Wait for an event by polling (knobs.poll, default on) instead of
 // hipEventSynchronize: a thread blocked in a HIP synchronisation call for a
 // 60-70 ms chunk-id kernel held up the other threads' launches (r5r: each
 // batch's chunking started only after the previous batch's ids were done).
-hipError_t wait_event(hipEvent_t ev) {
-    static const bool poll = !(getenv("RCDC_INGEST_POLL") && atoi(getenv("RCDC_INGEST_POLL")) == 0);
-    if (!poll) return hipEventSynchronize(ev);
+hipError_t wait_event(Ing *g, hipEvent_t ev) {
+    if (!g->knobs.poll) return hipEventSynchronize(ev);
     for (;;) {
         const hipError_t e = hipEventQuery(ev);
         if (e != hipErrorNotReady) return e;
@@ -529,7 +595,7 @@ void deliver(Ing *g, const std::shared_ptr<PackJob> &pj) {
     {
         std::lock_guard<std::mutex> lk(g->cb_mu);
         if (g->pack_cb) g->pack_cb(g->user, &p);
-        if (g->prof) {
+        if (g->knobs.prof) {
             if (g->tl_ids.size() <= pj->batch) g->tl_ids.resize(pj->batch + 1, 0);
             g->tl_ids[pj->batch] = std::max(g->tl_ids[pj->batch], now_s() - g->t_first);
         }
@@ -618,16 +684,16 @@ void waiter_main(Ing *g) {
             w = std::move(g->wait_q.front());
             g->wait_q.pop_front();
         }
-        // the pump enqueues the copy's last piece and its event later
-        while (!w.issued->load() && !g->err && !g->stop)
+        // the pump enqueues the copy's last piece and its event later; an
+        // item dropped here (error, stop) lets go of its event like any other
+        while (!w.done->issued.load() && !g->err && !g->stop)
             std::this_thread::sleep_for(std::chrono::microseconds(50));
-        if (!w.issued->load()) continue;
-        if (wait_event(w.ev) != hipSuccess) {
+        if (!w.done->issued.load()) continue;
+        if (wait_event(g, w.done->fin) != hipSuccess) {
             set_err(g, RCDC_ERR_INTERNAL, "pack copy-back failed");
             continue;
         }
-        (void)hipEventDestroy(w.ev);
-        if (g->prof) {
+        if (g->knobs.prof) {
             std::lock_guard<std::mutex> lk(g->cb_mu);
             if (g->tl_d2h.size() <= w.batch) g->tl_d2h.resize(w.batch + 1, 0);
             g->tl_d2h[w.batch] = now_s() - g->t_first;
@@ -651,7 +717,7 @@ void waiter_main(Ing *g) {
 
 // ---- stage A: one closed input slot becomes a batch in flight ------------
 void mark(Ing *g, uint64_t b, double t) {
-    if (!g->prof) return;
+    if (!g->knobs.prof) return;
     std::lock_guard<std::mutex> lk(g->cb_mu);
     if (g->tl.size() <= b) g->tl.resize(b + 1);
     g->tl[b].push_back(t - g->t_first);
@@ -685,11 +751,12 @@ bool submit_ready(Ing *g) {
         mark(g, B->index, now_s());
         PSlot &P = g->ps[ps];
         const uint64_t used = in->used;
-        if (!ensure_dev(g, &P.arena, &P.arena_cap, round_up(used, 256) + 512)) return false;
+        const uint64_t need = round_up(used, 256) + 512;
+        if (!P.arena.ensure(g, need, grow8(need), "arena")) return false;
         // the arena's previous batch is retired: its ids (the last reader)
         // are done.  The copy goes to the pump (feeder_main), piece by piece.
         in->h2d_issued = false;
-        g->h2d_q.push_back({P.arena, in->host, used, 0, in});
+        g->h2d_q.push_back({P.arena, in->host, used, 0, in, {}, nullptr});
         std::lock_guard<std::mutex> lk(g->mu);
         g->submitted.push_back(std::move(B));
         g->submitting--;
@@ -712,102 +779,95 @@ void close_open_locked(Ing *g);
 // waited ~40 ms (r5n: seal 40 ms after zstd; the next batch's stage A
 // started only after the previous chunk ids).  With two pieces in flight an
 // upload waits ~2.4 ms at most and the engine never idles.
-bool pump_h2d(Ing *g, std::deque<hipEvent_t> &inflight, std::vector<hipEvent_t> &free_ev) {
-    while (!inflight.empty() && hipEventQuery(inflight.front()) == hipSuccess) {
-        free_ev.push_back(inflight.front());
-        inflight.pop_front();
+//
+// The D2H of the pack bytes goes the same way (small read-backs of stage A
+// wait behind a whole 1 GiB pack copy otherwise: r5p, the next batch's
+// chunking started only when the previous batch's packs were in host memory).
+struct CopyLane {  // one direction's piece events: enqueued, and free
+    std::deque<Event> inflight;
+    std::vector<Event> free_ev;
+    hipError_t create() {
+        free_ev.resize(4);
+        for (Event &e : free_ev)
+            if (hipError_t r = e.create()) return r;
+        return hipSuccess;
     }
-    while (!g->h2d_q.empty() && inflight.size() < 2 && !free_ev.empty()) {
-        Ing::H2DJob &J = g->h2d_q.front();
-        const uint64_t n = std::min(g->copy_piece, J.len - J.done);
+};
+
+// One pump for both directions: pieces of the front job of `q` (under `mu`,
+// if it has one) go to stream `s`; `on_done` runs once a job's last piece is
+// enqueued.  A job's first piece waits on its `after` event, if it has one.
+template <typename Done>
+bool pump(Ing *g, hipStream_t s, std::deque<Ing::CopyJob> &q, std::mutex *mu, hipMemcpyKind kind,
+          CopyLane &L, Done on_done) {
+    while (!L.inflight.empty() && hipEventQuery(L.inflight.front()) == hipSuccess) {
+        L.free_ev.push_back(std::move(L.inflight.front()));
+        L.inflight.pop_front();
+    }
+    std::unique_lock<std::mutex> lq;
+    if (mu) lq = std::unique_lock<std::mutex>(*mu);
+    while (!q.empty() && L.inflight.size() < 2 && !L.free_ev.empty()) {
+        Ing::CopyJob &J = q.front();
+        if (J.after) {
+            ING_HIP(g, hipStreamWaitEvent(s, J.after, 0));
+            J.after.reset();
+        }
+        const uint64_t n = std::min(g->knobs.copy_piece, J.len - J.done);
         if (n) {
-            if (g->kcopy)
+            if (g->knobs.kcopy)
                 ING_HIP(g, launch_stream_copy(J.dst + J.done, J.src + J.done, (n + 15) & ~15ull,
-                                              g->kcopy, g->s_in));
+                                              g->knobs.kcopy, s));
             else
-                ING_HIP(g, hipMemcpyAsync(J.dst + J.done, J.src + J.done, n, hipMemcpyHostToDevice,
-                                          g->s_in));
-            hipEvent_t ev = free_ev.back();
-            free_ev.pop_back();
-            ING_HIP(g, hipEventRecord(ev, g->s_in));
-            inflight.push_back(ev);
+                ING_HIP(g, hipMemcpyAsync(J.dst + J.done, J.src + J.done, n, kind, s));
+            ING_HIP(g, hipEventRecord(L.free_ev.back(), s));
+            L.inflight.push_back(std::move(L.free_ev.back()));
+            L.free_ev.pop_back();
             J.done += n;
         }
         if (J.done == J.len) {
-            ING_HIP(g, hipEventRecord(J.in->h2d, g->s_in));
-            J.in->h2d_issued = true;
-            g->h2d_q.pop_front();
-            std::lock_guard<std::mutex> lk(g->mu);
-            g->cv_slot.notify_all();
+            if (!on_done(J)) return false;
+            q.pop_front();
         }
     }
     return true;
 }
 
-// The D2H of the pack bytes the same way (small read-backs of stage A wait
-// behind a whole 1 GiB pack copy otherwise: r5p, the next batch's chunking
-// started only when the previous batch's packs were in host memory).
-bool pump_d2h(Ing *g, std::deque<hipEvent_t> &inflight, std::vector<hipEvent_t> &free_ev) {
-    while (!inflight.empty() && hipEventQuery(inflight.front()) == hipSuccess) {
-        free_ev.push_back(inflight.front());
-        inflight.pop_front();
-    }
-    std::lock_guard<std::mutex> lq(g->d2h_mu);
-    while (!g->d2h_q.empty() && inflight.size() < 2 && !free_ev.empty()) {
-        Ing::D2HJob &J = g->d2h_q.front();
-        if (!J.waited) {
-            ING_HIP(g, hipStreamWaitEvent(g->s_out, J.after, 0));
-            ING_HIP(g, hipEventDestroy(J.after));
-            J.waited = true;
-        }
-        const uint64_t n = std::min(g->copy_piece, J.len - J.done);
-        if (n) {
-            if (g->kcopy)
-                ING_HIP(g, launch_stream_copy(J.dst + J.done, J.src + J.done, (n + 15) & ~15ull,
-                                              g->kcopy, g->s_out));
-            else
-                ING_HIP(g, hipMemcpyAsync(J.dst + J.done, J.src + J.done, n, hipMemcpyDeviceToHost,
-                                          g->s_out));
-            hipEvent_t ev = free_ev.back();
-            free_ev.pop_back();
-            ING_HIP(g, hipEventRecord(ev, g->s_out));
-            inflight.push_back(ev);
-            J.done += n;
-        }
-        if (J.done == J.len) {
-            ING_HIP(g, hipEventRecord(g->ev_out, g->s_out));
-            ING_HIP(g, hipEventRecord(J.fin, g->s_out));
-            J.issued->store(true);
-            g->d2h_q.pop_front();
-        }
-    }
-    return true;
+bool pump_h2d(Ing *g, CopyLane &L) {
+    return pump(g, g->s_in, g->h2d_q, nullptr, hipMemcpyHostToDevice, L, [g](Ing::CopyJob &J) {
+        ING_HIP(g, hipEventRecord(J.in->h2d, g->s_in));
+        J.in->h2d_issued = true;
+        std::lock_guard<std::mutex> lk(g->mu);
+        g->cv_slot.notify_all();
+        return true;
+    });
+}
+
+bool pump_d2h(Ing *g, CopyLane &L) {
+    return pump(g, g->s_out, g->d2h_q, &g->d2h_mu, hipMemcpyDeviceToHost, L, [g](Ing::CopyJob &J) {
+        ING_HIP(g, hipEventRecord(g->ev_out, g->s_out));
+        ING_HIP(g, hipEventRecord(J.fin->fin, g->s_out));
+        J.fin->issued.store(true);
+        return true;
+    });
 }
 
 void feeder_main(Ing *g) {
     (void)hipSetDevice(g->device);
-    std::deque<hipEvent_t> inflight, inflight_o;
-    std::vector<hipEvent_t> free_ev(4, nullptr), free_o(4, nullptr);
-    for (auto *v : {&free_ev, &free_o})
-        for (auto &e : *v)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-                set_err(g, RCDC_ERR_INTERNAL, "feeder events");
-                return;
-            }
-    auto release = [&] {
-        (void)hipStreamSynchronize(g->s_in);
-        (void)hipStreamSynchronize(g->s_out);
-        for (auto e : inflight) free_ev.push_back(e);
-        for (auto e : inflight_o) free_o.push_back(e);
-        for (auto e : free_ev) (void)hipEventDestroy(e);
-        for (auto e : free_o) (void)hipEventDestroy(e);
-    };
+    CopyLane in, out;
+    if (in.create() != hipSuccess || out.create() != hipSuccess) {
+        set_err(g, RCDC_ERR_INTERNAL, "feeder events");
+        return;
+    }
+    struct Drain {  // on every way out, before the lanes' events go
+        Ing *g;
+        ~Drain() {
+            (void)hipStreamSynchronize(g->s_in);
+            (void)hipStreamSynchronize(g->s_out);
+        }
+    } drain{g};
     for (;;) {
         reap_inputs(g);
-        if (!submit_ready(g) || !pump_h2d(g, inflight, free_ev) || !pump_d2h(g, inflight_o, free_o)) {
-            release();
-            return;
-        }
+        if (!submit_ready(g) || !pump_h2d(g, in) || !pump_d2h(g, out)) return;
         bool d2h_idle;
         {
             std::lock_guard<std::mutex> lq(g->d2h_mu);
@@ -819,11 +879,7 @@ void feeder_main(Ing *g) {
         if (g->open && !g->open->files.empty() && now_s() - g->open->t_first >= g->slot_max_age)
             close_open_locked(g);
         // the back thread queues D2H jobs until the very end (finalize)
-        if (g->err || (g->finished && g->h2d_q.empty() && d2h_idle)) {
-            lk.unlock();
-            release();
-            return;
-        }
+        if (g->err || (g->finished && g->h2d_q.empty() && d2h_idle)) return;
         // a piece is ~1.2 ms: poll often while copies are queued
         g->cv_slot.wait_for(lk, std::chrono::microseconds(g->h2d_q.empty() && d2h_idle ? 200 : 50));
     }
@@ -933,20 +989,25 @@ bool build_units(Ing *g, Batch *B, std::vector<rcdc_copy_ref> &cr, uint64_t *asm
     return true;
 }
 
-bool stage_a(Ing *g, Batch *B) {
+// ---- stage A, step by step (stage_a below runs them in this order) ---------
+
+// 1. The H2D (the feeder's pump) lands before the chunking: wait until its
+// event is enqueued, then order the compute stream after it.
+bool a_wait_h2d(Ing *g, Batch *B) {
     InSlot *in = B->in;
-    PSlot &P = g->ps[B->pslot];
-    const uint64_t used = in->used;
-    // 1. the H2D (the feeder's pump) lands before the chunking: wait until
-    // its event is enqueued, then order the compute stream after it
     {
         std::unique_lock<std::mutex> lk(g->mu);
         while (!in->h2d_issued && !g->err) g->cv_slot.wait_for(lk, std::chrono::microseconds(100));
         if (g->err) return false;
     }
     ING_HIP(g, hipStreamWaitEvent(g->s_comp, in->h2d, 0));
-    if (g->prof > 1) mark(g, B->index, now_s());
-    // 2. the plan streams; streams' carries and scattered pieces gathered
+    if (g->knobs.prof > 1) mark(g, B->index, now_s());
+    return true;
+}
+
+// 2. The plan streams; streams' carries and scattered pieces gathered.
+// *arena_len: the arena bytes the plan covers.
+bool a_gather_units(Ing *g, Batch *B, PSlot &P, uint64_t *arena_len) {
     std::vector<rcdc_copy_ref> gcr;
     uint64_t asm_used = 0;
     if (!build_units(g, B, gcr, &asm_used)) return false;
@@ -956,135 +1017,122 @@ bool stage_a(Ing *g, Batch *B) {
                                    g->s_comp),
                "stream gather");
     }
+    *arena_len = std::max(round_up(B->in->used, 256) + 256,
+                          asm_used ? g->asm_base + asm_used + 256 : 0);
+    return true;
+}
+
+// 3. Chunk: the slot's plan laid out for the units and run; `cuts` are
+// relative to each unit, counts[i] of them per unit, consecutive.
+bool a_chunk(Ing *g, Batch *B, PSlot &P, uint64_t arena_len, std::vector<uint64_t> &cuts,
+             std::vector<uint64_t> &counts) {
     const uint32_t nf = (uint32_t)B->units.size();
     std::vector<uint64_t> offs(nf), lens(nf);
-    uint64_t bytes = 0, ubytes = 0, nfiles = 0;
+    uint64_t ubytes = 0;
     for (uint32_t i = 0; i < nf; i++) {
         offs[i] = B->units[i].off;
         lens[i] = B->units[i].len;
-        bytes += B->units[i].fresh;
         ubytes += lens[i];
-        nfiles += !B->units[i].st || (B->units[i].final && !B->units[i].aborted);
     }
-    const uint64_t arena_len =
-        std::max(round_up(used, 256) + 256, asm_used ? g->asm_base + asm_used + 256 : 0);
-    // 3. chunk
     if (!P.plan) {
-        ING_ST(g, rcdc_plan_create(g->ctx, offs.data(), lens.data(), nf, arena_len, &P.plan),
-               "plan");
+        rcdc_plan *pl = nullptr;
+        ING_ST(g, rcdc_plan_create(g->ctx, offs.data(), lens.data(), nf, arena_len, &pl), "plan");
+        P.plan.reset(pl);
     } else {
-        ING_ST(g, plan_relayout(P.plan, offs.data(), lens.data(), nf, arena_len, g->s_comp),
+        ING_ST(g, plan_relayout(P.plan.get(), offs.data(), lens.data(), nf, arena_len, g->s_comp),
                "plan");
     }
-    if (g->prof > 1) mark(g, B->index, now_s());
-    ING_ST(g, rcdc_plan_run(P.plan, P.arena, g->s_comp), "chunk");
-    if (g->prof > 1) {  // (RCDC_INGEST_PROF=2: the H2D's and the chunking's own ends)
-        (void)hipEventSynchronize(in->h2d);
+    if (g->knobs.prof > 1) mark(g, B->index, now_s());
+    ING_ST(g, rcdc_plan_run(P.plan.get(), P.arena, g->s_comp), "chunk");
+    if (g->knobs.prof > 1) {  // (RCDC_INGEST_PROF=2: the H2D's and the chunking's own ends)
+        (void)hipEventSynchronize(B->in->h2d);
         mark(g, B->index, now_s());
     }
     const uint64_t cap = (uint64_t)nf + ubytes / 4096 + 16;  // min >= 4096 (rcdc_check_params)
-    std::vector<uint64_t> cuts(std::max<uint64_t>(cap, 1)), counts(std::max<uint32_t>(nf, 1));
-    rcdc_status rs = rcdc_plan_results(P.plan, cuts.data(), cuts.size(), counts.data());
+    cuts.assign(std::max<uint64_t>(cap, 1), 0);
+    counts.assign(std::max<uint32_t>(nf, 1), 0);
+    rcdc_status rs = rcdc_plan_results(P.plan.get(), cuts.data(), cuts.size(), counts.data());
     if (rs == RCDC_ERR_CAPACITY) {
         uint64_t tot = 0;
         for (uint32_t i = 0; i < nf; i++) tot += counts[i];
         cuts.resize(tot);
-        rs = rcdc_plan_results(P.plan, cuts.data(), cuts.size(), counts.data());
+        rs = rcdc_plan_results(P.plan.get(), cuts.data(), cuts.size(), counts.data());
     }
     ING_ST(g, rs, "chunk results");
     mark(g, B->index, now_s());
-    // chunk lists: a stream's last chunk of a batch (not its end) is its
-    // carry, not a chunk yet -- every earlier cut is final
-    B->ncuts.resize(nf);
-    std::vector<rcdc_copy_ref> ccr;  // the new carries, device
-    std::vector<std::pair<Unit *, uint64_t>> carries;  // (unit, carry start in the unit)
-    {
-        uint64_t k = 0;
-        for (uint32_t i = 0; i < nf; i++) {
-            Unit &u = B->units[i];
-            const uint64_t n = counts[i];
-            uint64_t keep = n;
-            if (u.st && (!u.final || u.aborted)) {
-                keep = n ? n - 1 : 0;
-                const uint64_t from = keep ? cuts[k + keep - 1] : 0;
-                if (!u.aborted) {
-                    carries.push_back({&u, from});
-                    if (u.len > from) {
-                        rcdc_copy_ref c{};
-                        c.in_off = u.off + from;
-                        c.out_off = (uint64_t)u.st->cslot * g->max_chunk;
-                        c.len = u.len - from;
-                        c.src = 0;
-                        ccr.push_back(c);
-                    }
-                }
-            }
-            B->ncuts[i] = (uint32_t)keep;
-            uint64_t prev = 0;
-            for (uint64_t j = 0; j < keep; j++) {
-                B->cuts.push_back(cuts[k + j]);
-                B->c_off.push_back(u.off + prev);
-                B->c_len.push_back(cuts[k + j] - prev);
-                prev = cuts[k + j];
-            }
-            k += n;
-        }
-    }
+    return true;
+}
+
+// 4. Cut lists (steps::cut_lists): the chunks final in this batch go into B;
+// returned with the streams' new carries and their device copies.
+steps::CutLists a_cut_lists(Ing *g, Batch *B, const std::vector<uint64_t> &cuts,
+                            const std::vector<uint64_t> &counts) {
+    std::vector<steps::UnitView> uv;
+    for (const Unit &u : B->units)
+        uv.push_back({u.st != nullptr, u.final, u.aborted, u.off, u.len, u.st ? u.st->cslot : 0});
+    steps::CutLists L = steps::cut_lists(uv, counts.data(), cuts.data(), g->max_chunk);
+    B->cuts = std::move(L.cuts);
+    B->ncuts = std::move(L.ncuts);
+    B->c_off = std::move(L.c_off);
+    B->c_len = std::move(L.c_len);
+    B->ids.assign(B->c_off.size() * 32, 0);
+    return L;
+}
+
+// 5. ids: short chunks on the device (own stream per pipeline slot), long
+// ones on host threads from the input slot.
+// 5a. The split.  The last batches' ids bound the run's end: a batch's
+// longest device chain (~34 MB/s per lane: 62 ms for a 2 MiB chunk) holds its
+// stage B, and stage B runs in batch order, so the host takes the chunks above
+// 1 MiB of the last knobs.tail_batches (default 2) batches too and both sides
+// end together (~30 ms).  (The last batch alone: the one before it still
+// waited ~40 ms for its device ids, r5y.)
+void a_split_ids(Ing *g, Batch *B, std::vector<uint32_t> &long_idx) {
     const uint64_t nchunks = B->c_off.size();
-    B->ids.assign(nchunks * 32, 0);
-    // 3. ids: short chunks on the device (own stream per pipeline slot), long
-    // ones on host threads from the input slot
-    // The last batches' ids bound the run's end: a batch's longest device
-    // chain (~34 MB/s per lane: 62 ms for a 2 MiB chunk) holds its stage B,
-    // and stage B runs in batch order, so the host takes the chunks above
-    // 1 MiB of the last RCDC_INGEST_TAIL_BATCHES (default 2) batches too and
-    // both sides end together (~30 ms).  (The last batch alone: the one
-    // before it still waited ~40 ms for its device ids, r5y.)
-    static const size_t tail_batches =
-        getenv("RCDC_INGEST_TAIL_BATCHES") ? (size_t)atoi(getenv("RCDC_INGEST_TAIL_BATCHES")) : 2;
     bool tail;
     {
         std::lock_guard<std::mutex> lk(g->mu);
         const size_t after = g->ready.size() + g->submitted.size() + (size_t)g->submitting +
                              (g->open != nullptr ? 1 : 0);
-        tail = g->finishing && after < tail_batches;
+        tail = g->finishing && after < g->knobs.tail_batches;
     }
     const uint64_t long_thr = tail ? std::min<uint64_t>(g->long_chunk, 1ull << 20) : g->long_chunk;
-    std::vector<uint32_t> long_idx;
     for (uint64_t k = 0; k < nchunks; k++)
         (B->c_len[k] > long_thr ? long_idx : B->short_idx).push_back((uint32_t)k);
     // the long chunks' host bytes: in place, or gathered from a stream's
     // host pieces (a chunk that starts in the carry) before the carries move
     B->c_host.assign(nchunks, nullptr);
-    if (!long_idx.empty()) {
-        std::vector<uint32_t> unit_of(nchunks);
-        for (uint32_t i = 0, k = 0; i < nf; i++)
-            for (uint32_t j = 0; j < B->ncuts[i]; j++) unit_of[k++] = i;
-        for (uint32_t k : long_idx) {
-            const Unit &u = B->units[unit_of[k]];
-            const uint64_t rel = B->c_off[k] - u.off;
-            B->c_host[k] = unit_host(u, rel, B->c_len[k]);
-            if (!B->c_host[k]) {
-                B->gathers.emplace_back(B->c_len[k]);
-                unit_gather(u, rel, B->c_len[k], B->gathers.back().data());
-                B->c_host[k] = B->gathers.back().data();
-            }
+    if (long_idx.empty()) return;
+    std::vector<uint32_t> unit_of(nchunks);
+    for (uint32_t i = 0, k = 0; i < B->units.size(); i++)
+        for (uint32_t j = 0; j < B->ncuts[i]; j++) unit_of[k++] = i;
+    for (uint32_t k : long_idx) {
+        const Unit &u = B->units[unit_of[k]];
+        const uint64_t rel = B->c_off[k] - u.off;
+        B->c_host[k] = unit_host(u, rel, B->c_len[k]);
+        if (!B->c_host[k]) {
+            B->gathers.emplace_back(B->c_len[k]);
+            unit_gather(u, rel, B->c_len[k], B->gathers.back().data());
+            B->c_host[k] = B->gathers.back().data();
         }
     }
-    // the streams' new carries (device: one copy; host: their bytes), and
-    // the carry slots of streams that ended
-    if (!ccr.empty()) {
+}
+
+// 5b. The streams' new carries (device: one copy; host: their bytes), and
+// the carry slots of streams that ended.
+bool a_move_carries(Ing *g, Batch *B, PSlot &P, const steps::CutLists &L) {
+    if (!L.copies.empty()) {
         const void *csrc[1] = {P.arena};
-        ING_ST(g, rcdc_copy_ranges(g->ctx, csrc, 1, ccr.data(), (uint32_t)ccr.size(), g->carry_pool,
-                                   g->s_comp),
+        ING_ST(g, rcdc_copy_ranges(g->ctx, csrc, 1, L.copies.data(), (uint32_t)L.copies.size(),
+                                   g->carry_pool, g->s_comp),
                "stream carry");
     }
     // A long chunk's host bytes may lie inside the old carry (c_host points
     // into it: a chunk of exactly max bytes that ended a batch's unit is
     // the next batch's carry, whole): the old carries stay with the batch
     // until its host id jobs are done (stage B runs after them)
-    for (auto &c : carries) {
-        Unit &u = *c.first;
+    for (const auto &c : L.carries) {
+        Unit &u = B->units[c.first];
         StreamSt &st = *u.st;
         std::vector<uint8_t> h(u.len - c.second);
         if (!h.empty()) unit_gather(u, c.second, h.size(), h.data());
@@ -1093,33 +1141,29 @@ bool stage_a(Ing *g, Batch *B) {
         st.base = u.base + c.second;
         st.carry_len = u.len - c.second;
     }
-    {
-        std::lock_guard<std::mutex> lk(g->mu);
-        for (Unit &u : B->units)
-            if (u.st && u.final && u.st->cslot >= 0) {
-                g->free_cslots.push_back(u.st->cslot);
-                u.st->cslot = -1;
-                B->gathers.push_back(std::move(u.st->hcarry));
-                u.st->hcarry = std::vector<uint8_t>();
-                g->closing_streams--;
-            }
-        g->cv_slot.notify_all();
-    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    for (Unit &u : B->units)
+        if (u.st && u.final && u.st->cslot >= 0) {
+            g->free_cslots.push_back(u.st->cslot);
+            u.st->cslot = -1;
+            B->gathers.push_back(std::move(u.st->hcarry));
+            u.st->hcarry = std::vector<uint8_t>();
+            g->closing_streams--;
+        }
+    g->cv_slot.notify_all();
+    return true;
+}
+
+// 5c. The short chunks' refs (longest first) up, and their ids on s_ids
+// after the compute stream's work so far.
+bool a_device_ids(Ing *g, Batch *B, PSlot &P) {
     std::sort(B->short_idx.begin(), B->short_idx.end(),
               [&](uint32_t a, uint32_t b) { return B->c_len[a] > B->c_len[b]; });
-    const uint64_t ns = B->short_idx.size();
-    if (ns > P.refs_cap) {
-        if (getenv("RCDC_ALLOC_LOG") && P.refs_cap)
-            fprintf(stderr, "rcdc ingest: regrow refs %llu -> %llu\n", (unsigned long long)P.refs_cap,
-                    (unsigned long long)ns);
-        ING_HIP(g, ing_free(&P.h_refs));
-        ING_HIP(g, ing_free(&P.d_refs));
-        ING_HIP(g, ing_free(&P.d_dig));
-        P.refs_cap = ns + ns / 4 + 64;
-        ING_HIP(g, ing_alloc(g, &P.h_refs, P.refs_cap * 16, true));
-        ING_HIP(g, ing_alloc(g, &P.d_refs, P.refs_cap * 16, false));
-        ING_HIP(g, ing_alloc(g, &P.d_dig, P.refs_cap * 32, false));
-    }
+    const uint64_t ns = B->short_idx.size(), grown = ns + ns / 4 + 64;  // the refs' headroom: a quarter
+    if (!P.h_refs.ensure(g, 2 * ns, 2 * grown, "refs (host)") ||
+        !P.d_refs.ensure(g, 2 * ns, 2 * grown, "refs") ||
+        !P.d_dig.ensure(g, 32 * ns, 32 * grown, "digests"))
+        return false;
     for (uint64_t j = 0; j < ns; j++) {
         P.h_refs[2 * j] = B->c_off[B->short_idx[j]];
         P.h_refs[2 * j + 1] = B->c_len[B->short_idx[j]];
@@ -1128,16 +1172,21 @@ bool stage_a(Ing *g, Batch *B) {
     ING_HIP(g, hipStreamWaitEvent(P.s_ids, g->ev_comp, 0));
     if (ns) {
         ING_HIP(g, hipMemcpyAsync(P.d_refs, P.h_refs, ns * 16, hipMemcpyHostToDevice, P.s_ids));
-        ING_ST(g, rcdc_sha256_chunks(g->ctx, P.arena, (const rcdc_chunk_ref *)P.d_refs,
+        ING_ST(g, rcdc_sha256_chunks(g->ctx, P.arena, (const rcdc_chunk_ref *)P.d_refs.p,
                                      (uint32_t)ns, P.d_dig, P.s_ids),
                "chunk ids");
     }
     ING_HIP(g, hipEventRecord(P.ev_ids, P.s_ids));
-    // long ids: groups of similar lengths (longest first), `ways` per call on
-    // the SHA extensions or 16 per multi-buffer call (sha_policy)
+    return true;
+}
+
+// 5d. Long ids: groups of similar lengths (longest first), `ways` per call on
+// the SHA extensions or 16 per multi-buffer call (sha_policy).  From here the
+// input slot is freed once its H2D and these jobs are done.
+void a_host_ids(Ing *g, Batch *bp, std::vector<uint32_t> &long_idx) {
+    InSlot *in = bp->in;
     std::sort(long_idx.begin(), long_idx.end(),
-              [&](uint32_t a, uint32_t b) { return B->c_len[a] > B->c_len[b]; });
-    Batch *bp = B;
+              [&](uint32_t a, uint32_t b) { return bp->c_len[a] > bp->c_len[b]; });
     const bool mb = sha_policy().mb;
     const size_t per = mb ? 16 : (size_t)sha_policy().ways;
     for (size_t a = 0; a < long_idx.size(); a += per) {
@@ -1162,13 +1211,18 @@ bool stage_a(Ing *g, Batch *B) {
             g->cv_slot.notify_all();
         }, true);
     }
-    {  // from here the slot is freed once its H2D and long-id jobs are done
-        std::lock_guard<std::mutex> lk(g->mu);
-        in->h2d_pending = true;
-        in->state = kSubmitted;
-    }
-    // 4. every chunk: zstd (version 2), seal into the staging area, verify
-    std::vector<uint64_t> src_off(nchunks), src_len(nchunks);
+    std::lock_guard<std::mutex> lk(g->mu);
+    in->h2d_pending = true;
+    in->state = kSubmitted;
+}
+
+// 6a. Every chunk: zstd (version 2), sealed into the staging area once its
+// previous batch has been packed.  src_len: the bytes sealed per chunk (its
+// frame, or the chunk as it is).
+bool a_seal(Ing *g, Batch *B, PSlot &P, std::vector<uint64_t> &src_len) {
+    const uint64_t nchunks = B->c_off.size();
+    std::vector<uint64_t> src_off(nchunks);
+    src_len.assign(nchunks, 0);
     const uint8_t *src = P.arena;
     B->ulen.assign(nchunks, 0);
     if (g->compress && nchunks) {
@@ -1181,7 +1235,7 @@ bool stage_a(Ing *g, Batch *B) {
             src_off[k] = fo;
             fo = round_up(fo + rcdc_zstd_bound(B->c_len[k]) + 48, 16);
         }
-        if (!ensure_dev(g, &g->frames, &g->frames_cap, fo + 64)) return false;
+        if (!g->frames.ensure(g, fo + 64, grow8(fo + 64), "frames")) return false;
         ING_ST(g, rcdc_zstd_compress(g->ctx, g->level, P.arena, zr.data(), (uint32_t)nchunks,
                                      g->frames, src_len.data(), g->s_comp),
                "zstd");
@@ -1211,89 +1265,117 @@ bool stage_a(Ing *g, Batch *B) {
         random_bytes(nonces.data(), nonces.size());
         for (uint64_t k = 0; k < nchunks; k++) memcpy(ar[k].nonce, nonces.data() + 16 * k, 16);
     }
-    if (!ensure_dev(g, &P.staging, &P.staging_cap, so + 64)) return false;
+    if (!P.staging.ensure(g, so + 64, grow8(so + 64), "staging")) return false;
     // the staging area's previous batch has been packed (stage B, s_back)
     ING_HIP(g, hipStreamWaitEvent(g->s_comp, P.ev_retired, 0));
     if (nchunks)
         ING_ST(g, rcdc_aead_seal(g->ctx, g->cfg.key, src, ar.data(), (uint32_t)nchunks, P.staging,
                                  g->s_comp),
                "seal");
-    if (g->verify && nchunks) {
-        // very_data (decrypt.rs:508-529): open (MAC) into the frames buffer,
-        // decode, compare with the chunk in place
-        std::vector<rcdc_aead_ref> orf(nchunks);
-        std::vector<rcdc_zstd_check_ref> cr(nchunks);
-        uint64_t po = 0;
-        for (uint64_t k = 0; k < nchunks; k++) {
-            orf[k].in_off = B->seal_off[k];
-            orf[k].len = B->seal_len[k];
-            orf[k].out_off = po;
-            cr[k].frame_off = po;
-            cr[k].frame_len = src_len[k];
-            cr[k].data_off = B->c_off[k];
-            cr[k].data_len = B->c_len[k];
-            po = round_up(po + src_len[k] + 16, 16);
-        }
-        if (!g->compress && !ensure_dev(g, &g->frames, &g->frames_cap, po + 64)) return false;
-        std::vector<uint32_t> stat(nchunks, 0);
-        ING_ST(g, rcdc_aead_open(g->ctx, g->cfg.key, P.staging, orf.data(), (uint32_t)nchunks,
-                                 g->frames, stat.data(), g->s_comp),
-               "verify open");
-        for (uint64_t k = 0; k < nchunks; k++)
-            if (stat[k]) {
-                set_err(g, RCDC_ERR_VERIFICATION, "Verifying data failed (MAC)");
-                return false;
-            }
-        ING_ST(g, rcdc_zstd_check(g->ctx, g->frames, P.arena, cr.data(), (uint32_t)nchunks,
-                                  g->compress ? 0u : RCDC_CHECK_STORED, stat.data(), g->s_comp),
-               "verify check");
-        for (uint64_t k = 0; k < nchunks; k++)
-            if (stat[k]) {
-                set_err(g, RCDC_ERR_VERIFICATION,
-                        "Verifying compressed data failed (extra_verify, decrypt.rs:516-526)");
-                return false;
-            }
+    return true;
+}
+
+// 6b. verify_data (decrypt.rs:508-529): open (MAC) into the frames buffer,
+// decode, compare with the chunk in place.
+bool a_verify(Ing *g, Batch *B, PSlot &P, const std::vector<uint64_t> &src_len) {
+    const uint64_t nchunks = B->c_off.size();
+    std::vector<rcdc_aead_ref> orf(nchunks);
+    std::vector<rcdc_zstd_check_ref> cr(nchunks);
+    uint64_t po = 0;
+    for (uint64_t k = 0; k < nchunks; k++) {
+        orf[k].in_off = B->seal_off[k];
+        orf[k].len = B->seal_len[k];
+        orf[k].out_off = po;
+        cr[k].frame_off = po;
+        cr[k].frame_len = src_len[k];
+        cr[k].data_off = B->c_off[k];
+        cr[k].data_len = B->c_len[k];
+        po = round_up(po + src_len[k] + 16, 16);
     }
+    if (!g->compress && !g->frames.ensure(g, po + 64, grow8(po + 64), "frames")) return false;
+    std::vector<uint32_t> stat(nchunks, 0);
+    ING_ST(g, rcdc_aead_open(g->ctx, g->cfg.key, P.staging, orf.data(), (uint32_t)nchunks,
+                             g->frames, stat.data(), g->s_comp),
+           "verify open");
+    for (uint64_t k = 0; k < nchunks; k++)
+        if (stat[k]) {
+            set_err(g, RCDC_ERR_VERIFICATION, "Verifying data failed (MAC)");
+            return false;
+        }
+    ING_ST(g, rcdc_zstd_check(g->ctx, g->frames, P.arena, cr.data(), (uint32_t)nchunks,
+                              g->compress ? 0u : RCDC_CHECK_STORED, stat.data(), g->s_comp),
+           "verify check");
+    for (uint64_t k = 0; k < nchunks; k++)
+        if (stat[k]) {
+            set_err(g, RCDC_ERR_VERIFICATION,
+                    "Verifying compressed data failed (extra_verify, decrypt.rs:516-526)");
+            return false;
+        }
+    return true;
+}
+
+// 7. Stats: bytes and files new in this batch (a stream counts at its end).
+void a_stats(Ing *g, Batch *B) {
+    uint64_t bytes = 0, nfiles = 0;
+    for (const Unit &u : B->units) {
+        bytes += u.fresh;
+        nfiles += !u.st || (u.final && !u.aborted);
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->st.bytes_in += bytes;
+    g->st.files += nfiles;
+    g->st.chunks += B->c_off.size();
+    g->st.batches++;
+}
+
+bool stage_a(Ing *g, Batch *B) {
+    PSlot &P = g->ps[B->pslot];
+    uint64_t arena_len = 0;
+    std::vector<uint64_t> cuts, counts, src_len;
+    std::vector<uint32_t> long_idx;
+    if (!a_wait_h2d(g, B)) return false;                                // 1
+    if (!a_gather_units(g, B, P, &arena_len)) return false;             // 2
+    if (!a_chunk(g, B, P, arena_len, cuts, counts)) return false;       // 3
+    const steps::CutLists L = a_cut_lists(g, B, cuts, counts);          // 4
+    a_split_ids(g, B, long_idx);                                        // 5
+    if (!a_move_carries(g, B, P, L)) return false;
+    if (!a_device_ids(g, B, P)) return false;
+    a_host_ids(g, B, long_idx);
+    if (!a_seal(g, B, P, src_len)) return false;                  // 6
+    if (g->verify && !B->c_off.empty() && !a_verify(g, B, P, src_len)) return false;
     ING_HIP(g, hipEventRecord(P.ev_sealed, g->s_comp));
     mark(g, B->index, now_s());
-    {
-        std::lock_guard<std::mutex> lk(g->mu);
-        g->st.bytes_in += bytes;
-        g->st.files += nfiles;
-        g->st.chunks += nchunks;
-        g->st.batches++;
-    }
+    a_stats(g, B);                                                      // 7
     return true;
 }
 
 // ---- stage B: dedup, per-file results, packs ------------------------------
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;  // stage B with no batch: close the open pack
 
-bool stage_b(Ing *g, Batch *B, bool finalize) {
-    const bool has_slot = B->pslot != kNoSlot;
-    PSlot &P = g->ps[has_slot ? B->pslot : 0];
-    const uint64_t n = B->c_len.size();
-    mark(g, B->index, now_s());
-    if (has_slot) {
-        ING_HIP(g, wait_event(P.ev_ids));
-        ING_HIP(g, hipStreamWaitEvent(g->s_back, P.ev_sealed, 0));
-    }
-    mark(g, B->index, now_s());
+// The stage B steps (stage_b below runs them in this order).
+
+// 1. The batch's ids: the device's read back into place beside the host's.
+bool b_read_ids(Ing *g, Batch *B, PSlot &P) {
     const uint64_t ns = B->short_idx.size();
-    if (ns) {
-        std::vector<uint8_t> dig(ns * 32);
-        // on the ids' own stream (not the legacy default stream's queue)
-        ING_HIP(g, hipMemcpyAsync(dig.data(), P.d_dig, ns * 32, hipMemcpyDeviceToHost, P.s_ids));
-        ING_HIP(g, hipEventRecord(P.ev_ids, P.s_ids));
-        ING_HIP(g, wait_event(P.ev_ids));
-        for (uint64_t j = 0; j < ns; j++)
-            memcpy(B->ids.data() + 32ull * B->short_idx[j], dig.data() + 32 * j, 32);
-    }
-    // Packer::add (packer.rs:304-315): the first occurrence of an id the
-    // index does not have is added, in chunk order
-    std::vector<uint8_t> is_new(n, 0);
-    std::vector<rcdc_pack_blob> nb;
-    nb.reserve(n);
+    if (!ns) return true;
+    std::vector<uint8_t> dig(ns * 32);
+    // on the ids' own stream (not the legacy default stream's queue)
+    ING_HIP(g, hipMemcpyAsync(dig.data(), P.d_dig, ns * 32, hipMemcpyDeviceToHost, P.s_ids));
+    ING_HIP(g, hipEventRecord(P.ev_ids, P.s_ids));
+    ING_HIP(g, wait_event(g, P.ev_ids));
+    for (uint64_t j = 0; j < ns; j++)
+        memcpy(B->ids.data() + 32ull * B->short_idx[j], dig.data() + 32 * j, 32);
+    return true;
+}
+
+// 2. Packer::add (packer.rs:304-315): the first occurrence of an id the
+// index does not have is added, in chunk order -- to B->blobs, after the open
+// pack's blobs.  Returns the number added.
+size_t b_dedup(Ing *g, Batch *B, std::vector<uint8_t> &is_new) {
+    const uint64_t n = B->c_len.size();
+    is_new.assign(n, 0);
+    B->blobs = g->carry_blobs;
+    B->blobs.reserve(B->blobs.size() + n);
     for (uint64_t k = 0; k < n; k++) {
         Id32 id;
         memcpy(id.b, B->ids.data() + 32 * k, 32);
@@ -1306,195 +1388,155 @@ bool stage_b(Ing *g, Batch *B, bool finalize) {
         b.type = 0;
         b.pad = kSrcStaging;
         memcpy(b.id, id.b, 32);
-        nb.push_back(b);
+        B->blobs.push_back(b);
     }
-    // per-file results (the tree's content lists, file_archiver.rs:144-168):
-    // a whole file at once; a stream's chunks accumulate until its end
-    {
-        uint64_t k = 0;
-        for (size_t i = 0; i < B->units.size(); i++) {
-            const Unit &u = B->units[i];
-            const uint32_t ne = B->ncuts[i];
-            uint32_t nnew = 0;
-            for (uint32_t j = 0; j < ne; j++) nnew += is_new[k + j];
-            rcdc_ingest_file_result fr{};
-            bool deliver_file = false;
-            if (!u.st) {
-                fr.tag = u.tag;
-                fr.len = u.len;
-                fr.nchunks = ne;
-                fr.nnew = nnew;
-                fr.cuts = B->cuts.data() + k;
-                fr.ids = B->ids.data() + 32 * k;
+    return B->blobs.size() - g->carry_blobs.size();
+}
+
+// 3. Per-file results (the tree's content lists, file_archiver.rs:144-168):
+// a whole file at once; a stream's chunks accumulate until its end.
+void b_file_results(Ing *g, Batch *B, const std::vector<uint8_t> &is_new) {
+    uint64_t k = 0;
+    for (size_t i = 0; i < B->units.size(); i++) {
+        const Unit &u = B->units[i];
+        const uint32_t ne = B->ncuts[i];
+        uint32_t nnew = 0;
+        for (uint32_t j = 0; j < ne; j++) nnew += is_new[k + j];
+        rcdc_ingest_file_result fr{};
+        bool deliver_file = false;
+        if (!u.st) {
+            fr.tag = u.tag;
+            fr.len = u.len;
+            fr.nchunks = ne;
+            fr.nnew = nnew;
+            fr.cuts = B->cuts.data() + k;
+            fr.ids = B->ids.data() + 32 * k;
+            deliver_file = true;
+        } else {
+            StreamSt &st = *u.st;
+            for (uint32_t j = 0; j < ne; j++) st.cuts.push_back(u.base + B->cuts[k + j]);
+            st.ids.insert(st.ids.end(), B->ids.begin() + 32 * k, B->ids.begin() + 32 * (k + ne));
+            st.nnew += nnew;
+            if (u.final && !u.aborted) {
+                fr.tag = st.tag;
+                fr.len = u.base + u.len;  // the stream's length (its last cut)
+                fr.nchunks = (uint32_t)st.cuts.size();
+                fr.nnew = st.nnew;
+                fr.cuts = st.cuts.data();
+                fr.ids = st.ids.data();
                 deliver_file = true;
-            } else {
-                StreamSt &st = *u.st;
-                for (uint32_t j = 0; j < ne; j++) st.cuts.push_back(u.base + B->cuts[k + j]);
-                st.ids.insert(st.ids.end(), B->ids.begin() + 32 * k, B->ids.begin() + 32 * (k + ne));
-                st.nnew += nnew;
-                if (u.final && !u.aborted) {
-                    fr.tag = st.tag;
-                    fr.len = u.base + u.len;  // the stream's length (its last cut)
-                    fr.nchunks = (uint32_t)st.cuts.size();
-                    fr.nnew = st.nnew;
-                    fr.cuts = st.cuts.data();
-                    fr.ids = st.ids.data();
-                    deliver_file = true;
-                }
-            }
-            k += ne;
-            if (deliver_file && g->file_cb) {
-                std::lock_guard<std::mutex> lk(g->cb_mu);
-                g->file_cb(g->user, &fr);
-            }
-            if (u.st && u.final) {
-                std::vector<uint64_t>().swap(u.st->cuts);
-                std::vector<uint8_t>().swap(u.st->ids);
             }
         }
-    }
-    // the open pack's blobs first, then this batch's new ones
-    std::vector<rcdc_pack_blob> blobs = g->carry_blobs;
-    blobs.insert(blobs.end(), nb.begin(), nb.end());
-    // should_save (packer.rs:659-671) pack by pack; take_data adds each closed
-    // pack's size to the sizer (:749-758)
-    // ... and by age (MAX_AGE, packer.rs:63,668-670): the open pack carried in
-    // from earlier batches is saved once its first blob is pack_max_age old
-    const double tnow = now_s();
-    const bool carried = !g->carry_blobs.empty();
-    const bool aged = carried && tnow - g->pack_t0 >= g->pack_max_age;
-    std::vector<std::pair<uint32_t, uint32_t>> grp;
-    size_t b0 = 0;
-    while (b0 < blobs.size()) {
-        const uint64_t limit = g->sizer.pack_size();
-        uint64_t sz = 0, hdr = 0;
-        size_t e = b0;
-        while (e < blobs.size() && sz < limit && e - b0 < kMaxPackCount) {
-            sz += blobs[e].len;
-            hdr += blobs[e].uncompressed_len ? 41 : 37;
-            e++;
+        k += ne;
+        if (deliver_file && g->file_cb) {
+            std::lock_guard<std::mutex> lk(g->cb_mu);
+            g->file_cb(g->user, &fr);
         }
-        const bool closed = sz >= limit || e - b0 >= kMaxPackCount;
-        if (!closed && !finalize && !(aged && b0 == 0)) break;
-        grp.push_back({(uint32_t)b0, (uint32_t)(e - b0)});
-        g->sizer.current += sz + hdr + 32 + 4;
-        b0 = e;
-    }
-    const size_t open_from = b0;
-    std::vector<rcdc_pack> packs(grp.size());
-    uint64_t total = 0;
-    {
-        std::vector<uint8_t> hn(16 * grp.size());
-        random_bytes(hn.data(), hn.size());
-        for (size_t j = 0; j < grp.size(); j++) {
-            uint64_t sz = 32 + 4;
-            for (uint32_t i = grp[j].first; i < grp[j].first + grp[j].second; i++)
-                sz += blobs[i].len + (blobs[i].uncompressed_len ? 41 : 37);
-            packs[j].out_off = total;
-            packs[j].blob0 = grp[j].first;
-            packs[j].nblobs = grp[j].second;
-            memcpy(packs[j].header_nonce, hn.data() + 16 * j, 16);
-            total += sz;
+        if (u.st && u.final) {
+            std::vector<uint64_t>().swap(u.st->cuts);
+            std::vector<uint8_t>().swap(u.st->ids);
         }
     }
+}
+
+// The sources of the pack build and of the open pack's copy: [kSrcStaging]
+// the slot's staging area, [kSrcCarry] the current carry buffer (the carry
+// for both when there is no batch).
+void pack_sources(Ing *g, const Batch *B, const void *srcs[2]) {
+    const bool has_slot = B->pslot != kNoSlot;
+    const void *staging = g->ps[has_slot ? B->pslot : 0].staging;
     const void *cur_carry = g->carry[g->carry_cur];
-    const void *srcs[2] = {has_slot ? (const void *)P.staging : cur_carry,
-                           cur_carry ? cur_carry : (const void *)P.staging};
-    std::vector<uint32_t> boffs(std::max<size_t>(open_from, 1));
-    OutSlot *out = nullptr;
-    // The packs go back in groups of whole packs of ~256 MiB, each with its
-    // own end event: a group's pack ids start as soon as it has landed, not
-    // after the batch's whole D2H (~20 ms for a 2 GiB batch's ~1 GB of packs;
-    // the last batch's ids end the run).
-    struct D2HGroup {
-        size_t first, last;  // packs [first, last)
-        hipEvent_t fin;
-        std::shared_ptr<std::atomic<bool>> flag;
-    };
-    std::vector<D2HGroup> d2h_groups;
-    if (!grp.empty()) {
-        // the last pack build's D2H must be done with d_packs: once the pump
-        // has enqueued its last piece, ev_out marks its end
-        if (g->last_d2h)
-            while (!g->last_d2h->load() && !g->err)
-                std::this_thread::sleep_for(std::chrono::microseconds(50));
-        if (g->err) return false;
-        if (total + 64 > g->d_packs_cap) {
-            // a regrow frees d_packs: every D2H piece reading it must have
-            // run, not only been enqueued (hipFree waits for queued work, but
-            // the pump enqueues pieces one by one)
-            ING_HIP(g, wait_event(g->ev_out));
-            if (!ensure_dev(g, &g->d_packs, &g->d_packs_cap, total + 64)) return false;
-        }
-        ING_HIP(g, hipStreamWaitEvent(g->s_back, g->ev_out, 0));
-        ING_ST(g, rcdc_pack_build_raw_multi(g->ctx, g->cfg.key, srcs, 2, blobs.data(),
-                                            (uint32_t)open_from, packs.data(),
-                                            (uint32_t)packs.size(), g->d_packs, total,
-                                            boffs.data(), g->s_back),
-               "pack build");
-        {  // a free page-locked output slot
-            std::unique_lock<std::mutex> lk(g->mu);
-            for (;;) {
-                for (auto &o : g->outs)
-                    if (!o->busy) {
-                        out = o.get();
-                        break;
-                    }
-                if (out || g->err) break;
-                g->cv_slot.wait_for(lk, std::chrono::milliseconds(2));
-            }
-            if (!out) return false;
-            out->busy = true;
-        }
-        if (out->cap < total) {
-            if (getenv("RCDC_ALLOC_LOG") && out->cap)
-                fprintf(stderr, "rcdc ingest: regrow out slot %llu -> %llu\n",
-                        (unsigned long long)out->cap, (unsigned long long)total);
-            ING_HIP(g, ing_free(&out->host));
-            out->cap = total + total / 4;
-            ING_HIP(g, ing_alloc(g, &out->host, out->cap, true));
-        }
-        // the D2H goes to the feeder's pump, piece by piece, after the build
-        // (the first group's job orders the copy stream after it; the rest
-        // follow on that stream)
-        hipEvent_t after;
-        ING_HIP(g, hipEventCreateWithFlags(&after, hipEventDisableTiming));
-        ING_HIP(g, hipEventRecord(after, g->s_back));
-        static const uint64_t group_bytes_env =
-            getenv("RCDC_INGEST_D2H_GROUP") ? strtoull(getenv("RCDC_INGEST_D2H_GROUP"), nullptr, 10)
-                                            : 256ull << 20;
-        // The last two batches' packs go back one pack per group: each pack's
-        // id starts as soon as that pack has landed.  Their ids are the end of
-        // the run, and in groups of ~256 MiB the last group's packs were
-        // still being hashed ~43 ms after the last copy (r6i timeline, 16
-        // files: landed 385 ms, last id 429 ms).
-        static const bool tail_single =
-            !(getenv("RCDC_INGEST_TAIL_SINGLE") && atoi(getenv("RCDC_INGEST_TAIL_SINGLE")) == 0);
-        bool tail_b;
-        {
-            std::lock_guard<std::mutex> lk(g->mu);
-            tail_b = finalize || (g->finishing && g->front_done && g->inflight.size() <= 1);
-        }
-        const uint64_t group_bytes = tail_single && tail_b ? 1 : group_bytes_env;
-        for (size_t a = 0; a < grp.size();) {
-            size_t b = a + 1;
-            while (b < grp.size() && packs[b].out_off - packs[a].out_off < group_bytes) b++;
-            D2HGroup G{a, b, nullptr, std::make_shared<std::atomic<bool>>(false)};
-            ING_HIP(g, hipEventCreateWithFlags(&G.fin, hipEventDisableTiming));
-            const uint64_t lo = packs[a].out_off, hi = b < grp.size() ? packs[b].out_off : total;
-            {
-                std::lock_guard<std::mutex> lq(g->d2h_mu);
-                g->d2h_q.push_back({out->host + lo, g->d_packs + lo, hi - lo, 0,
-                                    a == 0 ? after : nullptr, G.fin, G.flag, a != 0});
-            }
-            g->last_d2h = G.flag;
-            d2h_groups.push_back(G);
-            a = b;
-        }
-        g->cv_slot.notify_all();
+    srcs[0] = has_slot ? staging : cur_carry;
+    srcs[1] = cur_carry ? cur_carry : staging;
+}
+
+// 6a. The closed packs built in d_packs.
+bool b_build_packs(Ing *g, Batch *B) {
+    // the last pack build's D2H must be done with d_packs: once the pump
+    // has enqueued its last piece, ev_out marks its end
+    if (g->last_d2h)
+        while (!g->last_d2h->issued.load() && !g->err)
+            std::this_thread::sleep_for(std::chrono::microseconds(50));
+    if (g->err) return false;
+    if (g->d_packs.cap < B->total + 64) {
+        // a regrow frees d_packs: every D2H piece reading it must have
+        // run, not only been enqueued (hipFree waits for queued work, but
+        // the pump enqueues pieces one by one)
+        ING_HIP(g, wait_event(g, g->ev_out));
+        if (!g->d_packs.ensure(g, B->total + 64, grow8(B->total + 64), "packs")) return false;
     }
-    // the still open pack: its blobs into the other carry buffer
-    std::vector<rcdc_pack_blob> rest(blobs.begin() + open_from, blobs.end());
+    ING_HIP(g, hipStreamWaitEvent(g->s_back, g->ev_out, 0));
+    const void *srcs[2];
+    pack_sources(g, B, srcs);
+    B->boffs.assign(std::max<size_t>(B->open_from, 1), 0);
+    ING_ST(g, rcdc_pack_build_raw_multi(g->ctx, g->cfg.key, srcs, 2, B->blobs.data(),
+                                        (uint32_t)B->open_from, B->packs.data(),
+                                        (uint32_t)B->packs.size(), g->d_packs, B->total,
+                                        B->boffs.data(), g->s_back),
+           "pack build");
+    return true;
+}
+
+// 6b. A free page-locked output slot, and the D2H to it queued for the
+// feeder's pump, piece by piece, after the build (the first group's job
+// orders the copy stream after it; the rest follow on that stream).
+// The packs go back in groups of whole packs of ~256 MiB, each with its
+// own end event: a group's pack ids start as soon as it has landed, not
+// after the batch's whole D2H (~20 ms for a 2 GiB batch's ~1 GB of packs;
+// the last batch's ids end the run).
+bool b_queue_d2h(Ing *g, Batch *B, bool finalize) {
+    OutSlot *out = nullptr;
+    {
+        std::unique_lock<std::mutex> lk(g->mu);
+        for (;;) {
+            for (auto &o : g->outs)
+                if (!o->busy) {
+                    out = o.get();
+                    break;
+                }
+            if (out || g->err) break;
+            g->cv_slot.wait_for(lk, std::chrono::milliseconds(2));
+        }
+        if (!out) return false;
+        out->busy = true;
+    }
+    B->out = out;
+    if (!out->host.ensure(g, B->total, B->total + B->total / 4, "out slot")) return false;
+    Event after;
+    ING_HIP(g, after.create());
+    ING_HIP(g, hipEventRecord(after, g->s_back));
+    // The last two batches' packs go back one pack per group: each pack's
+    // id starts as soon as that pack has landed.  Their ids are the end of
+    // the run, and in groups of ~256 MiB the last group's packs were
+    // still being hashed ~43 ms after the last copy (r6i timeline, 16
+    // files: landed 385 ms, last id 429 ms).
+    bool tail_b;
+    {
+        std::lock_guard<std::mutex> lk(g->mu);
+        tail_b = finalize || (g->finishing && g->front_done && g->inflight.size() <= 1);
+    }
+    const uint64_t group_bytes = g->knobs.tail_single && tail_b ? 1 : g->knobs.d2h_group;
+    for (const steps::D2HRange &r :
+         steps::d2h_ranges(B->packs.data(), B->packs.size(), B->total, group_bytes)) {
+        auto done = std::make_shared<D2HDone>();
+        ING_HIP(g, done->fin.create());
+        {
+            std::lock_guard<std::mutex> lq(g->d2h_mu);
+            g->d2h_q.push_back({out->host + r.lo, g->d_packs + r.lo, r.hi - r.lo, 0, nullptr,
+                                r.first == 0 ? std::move(after) : Event(), done});
+        }
+        g->last_d2h = done;
+        B->d2h.push_back({r, done});
+    }
+    g->cv_slot.notify_all();
+    return true;
+}
+
+// 7. The still open pack: its blobs into the other carry buffer.  Its age
+// runs from its first blob (a pack that starts in this batch is new; one
+// carried on keeps its time).
+bool b_carry_open_pack(Ing *g, Batch *B, bool carried, double tnow) {
+    std::vector<rcdc_pack_blob> rest(B->blobs.begin() + B->open_from, B->blobs.end());
     if (!rest.empty()) {
         const int nx = g->carry_cur ^ 1;
         std::vector<rcdc_copy_ref> cr(rest.size());
@@ -1508,60 +1550,106 @@ bool stage_b(Ing *g, Batch *B, bool finalize) {
             rest[i].pad = kSrcCarry;
             o = round_up(o + rest[i].len, 16);
         }
-        if (!ensure_dev(g, &g->carry[nx], &g->carry_cap[nx], o + 64)) return false;
+        if (!g->carry[nx].ensure(g, o + 64, grow8(o + 64), "carry")) return false;
+        const void *srcs[2];
+        pack_sources(g, B, srcs);
         ING_ST(g, rcdc_copy_ranges(g->ctx, srcs, 2, cr.data(), (uint32_t)cr.size(), g->carry[nx],
                                    g->s_back),
                "carry");
         g->carry_cur = nx;
     }
-    // the open pack's age: from its first blob (a pack that starts in this
-    // batch is new; one carried on keeps its time)
-    if (!rest.empty() && (open_from > 0 || !carried)) g->pack_t0 = tnow;
+    if (!rest.empty() && (B->open_from > 0 || !carried)) g->pack_t0 = tnow;
     g->carry_blobs = std::move(rest);
-    if (!grp.empty()) {
-        std::vector<std::shared_ptr<PackJob>> jobs;
-        for (size_t j = 0; j < grp.size(); j++) {
-            auto pj = std::make_shared<PackJob>();
-            pj->out = out;
-            pj->off = packs[j].out_off;
-            pj->size = packs[j].size;
-            pj->header_len = packs[j].header_len;
-            pj->seq = g->next_seq++;
-            pj->batch = B->index;
-            for (uint32_t i = grp[j].first; i < grp[j].first + grp[j].second; i++) {
-                rcdc_ingest_blob e{};
-                memcpy(e.id, blobs[i].id, 32);
-                e.offset = boffs[i];
-                e.length = blobs[i].len;
-                e.uncompressed_length = blobs[i].uncompressed_len;
-                e.type = blobs[i].type;
-                pj->blobs.push_back(e);
-            }
-            jobs.push_back(pj);
+    return true;
+}
+
+// 8. The packs' jobs: one wait item per D2H group for the waiter, which
+// hands the group's packs to the pool once they have landed.
+void b_post_packs(Ing *g, Batch *B) {
+    std::vector<std::shared_ptr<PackJob>> jobs;
+    for (size_t j = 0; j < B->grp.size(); j++) {
+        auto pj = std::make_shared<PackJob>();
+        pj->out = B->out;
+        pj->off = B->packs[j].out_off;
+        pj->size = B->packs[j].size;
+        pj->header_len = B->packs[j].header_len;
+        pj->seq = g->next_seq++;
+        pj->batch = B->index;
+        for (uint32_t i = B->grp[j].first; i < B->grp[j].first + B->grp[j].second; i++) {
+            rcdc_ingest_blob e{};
+            memcpy(e.id, B->blobs[i].id, 32);
+            e.offset = B->boffs[i];
+            e.length = B->blobs[i].len;
+            e.uncompressed_length = B->blobs[i].uncompressed_len;
+            e.type = B->blobs[i].type;
+            pj->blobs.push_back(e);
         }
-        out->packs_left += (int)jobs.size();
-        g->packs_pending += (int)jobs.size();
-        {
-            std::lock_guard<std::mutex> lk(g->mu);
-            g->st.packs += jobs.size();
-            g->st.pack_bytes += total;
-        }
-        {
-            std::lock_guard<std::mutex> lk(g->wait_mu);
-            for (const D2HGroup &G : d2h_groups)
-                g->wait_q.push_back({G.fin, G.flag, B->index,
-                                     std::vector<std::shared_ptr<PackJob>>(
-                                         jobs.begin() + G.first, jobs.begin() + G.last)});
-        }
-        g->wait_cv.notify_one();
+        jobs.push_back(pj);
     }
+    B->out->packs_left += (int)jobs.size();
+    g->packs_pending += (int)jobs.size();
+    {
+        std::lock_guard<std::mutex> lk(g->mu);
+        g->st.packs += jobs.size();
+        g->st.pack_bytes += B->total;
+    }
+    {
+        std::lock_guard<std::mutex> lk(g->wait_mu);
+        for (auto &d : B->d2h)
+            g->wait_q.push_back({d.second, B->index,
+                                 std::vector<std::shared_ptr<PackJob>>(
+                                     jobs.begin() + d.first.first, jobs.begin() + d.first.last)});
+    }
+    g->wait_cv.notify_one();
+}
+
+bool stage_b(Ing *g, Batch *B, bool finalize) {
+    const bool has_slot = B->pslot != kNoSlot;
+    PSlot &P = g->ps[has_slot ? B->pslot : 0];
+    mark(g, B->index, now_s());
+    if (has_slot) {                                                     // 1
+        ING_HIP(g, wait_event(g, P.ev_ids));
+        ING_HIP(g, hipStreamWaitEvent(g->s_back, P.ev_sealed, 0));
+    }
+    mark(g, B->index, now_s());
+    if (!b_read_ids(g, B, P)) return false;
+    std::vector<uint8_t> is_new;
+    const size_t nnew = b_dedup(g, B, is_new);                          // 2
+    b_file_results(g, B, is_new);                                       // 3
+    // 4. should_save pack by pack over the open pack's blobs and the new
+    // ones (steps::group_packs), and by age (MAX_AGE, packer.rs:63,668-670):
+    // the open pack carried in from earlier batches is saved once its first
+    // blob is pack_max_age old
+    const double tnow = now_s();
+    const bool carried = !g->carry_blobs.empty();
+    const bool aged = carried && tnow - g->pack_t0 >= g->pack_max_age;
+    B->grp = steps::group_packs(B->blobs.data(), B->blobs.size(), g->sizer, finalize, aged,
+                                &B->open_from);
+    // 5. the packs' places in the pack buffer, and their header nonces
+    B->packs.assign(B->grp.size(), rcdc_pack{});
+    B->total = steps::layout_packs(B->blobs.data(), B->grp, B->packs.data());
+    std::vector<uint8_t> hn(16 * B->grp.size());
+    random_bytes(hn.data(), hn.size());
+    for (size_t j = 0; j < B->grp.size(); j++) memcpy(B->packs[j].header_nonce, hn.data() + 16 * j, 16);
+    if (!B->grp.empty() && (!b_build_packs(g, B) || !b_queue_d2h(g, B, finalize))) return false;  // 6
+    if (!b_carry_open_pack(g, B, carried, tnow)) return false;          // 7
+    if (!B->grp.empty()) b_post_packs(g, B);                            // 8
     if (has_slot) ING_HIP(g, hipEventRecord(P.ev_retired, g->s_back));
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        g->st.new_blobs += nb.size();
+        g->st.new_blobs += nnew;
     }
     mark(g, B->index, now_s());
     return true;
+}
+
+// Stage B with no batch: the open pack is closed on its own (MAX_AGE with no
+// batch coming, or Packer::finalize with nothing else left).
+bool close_open_pack(Ing *g) {
+    Batch empty;
+    empty.pslot = kNoSlot;
+    empty.index = g->nbatches;
+    return stage_b(g, &empty, true);
 }
 
 // The input slot of a batch is free again once its H2D has landed and the
@@ -1572,11 +1660,7 @@ void reap_inputs(Ing *g) {
         if (s->state == kSubmitted && s->host_jobs == 0 &&
             (!s->h2d_pending || hipEventQuery(s->h2d) == hipSuccess)) {
             s->h2d_pending = false;
-            s->state = kFree;
-            s->used = 0;
-            s->files.clear();
-            s->has_stream = false;
-            s->t_first = 0;
+            s->reset(kFree);
             g->cv_slot.notify_all();
         }
 }
@@ -1655,10 +1739,7 @@ void back_main(Ing *g) {
             }
         }
         if (aged) {
-            Batch empty;
-            empty.pslot = kNoSlot;
-            empty.index = g->nbatches;
-            if (!stage_b(g, &empty, true)) return;
+            if (!close_open_pack(g)) return;
             continue;
         }
         if (B) {
@@ -1669,12 +1750,7 @@ void back_main(Ing *g) {
             continue;
         }
         if (all_done) {
-            if (fin_carry) {  // Packer::finalize with nothing else left
-                Batch empty;
-                empty.pslot = kNoSlot;
-                empty.index = g->nbatches;
-                if (!stage_b(g, &empty, true)) return;
-            }
+            if (fin_carry && !close_open_pack(g)) return;  // Packer::finalize
             std::unique_lock<std::mutex> lk(g->mu);
             g->finished = true;
             g->cv_done.notify_all();
@@ -1697,11 +1773,7 @@ void promote_locked(Ing *g) {
             bool empty = true;
             for (const FileEnt &f : s->files) empty &= f.cancelled;
             if (empty) {
-                s->state = kFree;
-                s->used = 0;
-                s->files.clear();
-                s->has_stream = false;
-                s->t_first = 0;
+                s->reset(kFree);
             } else {
                 g->ready.push_back(s);
             }
@@ -1736,7 +1808,7 @@ rcdc_status reserve_locked(Ing *g, std::unique_lock<std::mutex> &lk, uint64_t le
         InSlot *s = g->open;
         // the first slot closes at a quarter: the device starts sooner
         const uint64_t cap_now = g->nclosed == 0 ? std::max(g->batch_cap / 4, len)
-                                                 : (s ? s->cap : 0);
+                                                 : (s ? s->host.cap : 0);
         uint64_t place = s ? s->used : 0;
         if (s && st && !s->files.empty()) {
             const FileEnt &b = s->files.back();
@@ -1755,11 +1827,7 @@ rcdc_status reserve_locked(Ing *g, std::unique_lock<std::mutex> &lk, uint64_t le
                     break;
                 }
             if (s) {
-                s->state = kOpen;
-                s->used = 0;
-                s->files.clear();
-                s->has_stream = false;
-                s->t_first = 0;
+                s->reset(kOpen);
                 g->open = s;
             }
         }
@@ -1868,41 +1936,112 @@ Sizes engine_sizes(const rcdc_ctx *ctx, const rcdc_ingest_config *cfg, uint64_t 
     return z;
 }
 
-// Every buffer, stream, event and plan of the engine (threads stopped or
-// never started); safe on a partly built engine.
-void free_all(Ing *g) {
-    (void)hipSetDevice(g->device);
-    for (auto &s : g->in) {
-        (void)ing_free(&s->host);
-        if (s->h2d) (void)hipEventDestroy(s->h2d);
-        s->h2d = nullptr;
-    }
-    for (auto &o : g->outs) (void)ing_free(&o->host);
-    for (auto &P : g->ps) {
-        if (P.plan) rcdc_plan_destroy(P.plan);
-        P.plan = nullptr;
-        (void)ing_free(&P.arena);
-        (void)ing_free(&P.staging);
-        (void)ing_free(&P.d_refs);
-        (void)ing_free(&P.d_dig);
-        (void)ing_free(&P.h_refs);
-        for (hipEvent_t *e : {&P.ev_ids, &P.ev_sealed, &P.ev_retired})
-            if (*e) (void)hipEventDestroy(*e), *e = nullptr;
-        if (P.s_ids) (void)hipStreamDestroy(P.s_ids);
-        P.s_ids = nullptr;
-    }
-    (void)ing_free(&g->frames);
-    (void)ing_free(&g->d_packs);
-    (void)ing_free(&g->carry[0]);
-    (void)ing_free(&g->carry[1]);
-    (void)ing_free(&g->carry_pool);
-    for (hipStream_t *q : {&g->s_in, &g->s_comp, &g->s_out, &g->s_back})
-        if (*q) (void)hipStreamDestroy(*q), *q = nullptr;
-    for (hipEvent_t *e : {&g->ev_comp, &g->ev_back, &g->ev_out})
-        if (*e) (void)hipEventDestroy(*e), *e = nullptr;
-    if (g->own_idx) delete g->idx;
-    g->idx = nullptr;
+// create's failures: nothing to free by hand (the engine's owners do it)
+rcdc_status create_fail(hipError_t e, const char *what) {
+    return set_error(RCDC_ERR_INTERNAL, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
 }
+#define NEW_TRY(expr, what)                                         \
+    do {                                                            \
+        hipError_t e_ = (expr);                                     \
+        if (e_ != hipSuccess) return create_fail(e_, what);         \
+    } while (0)
+
+// One pipeline slot's stream, events, buffers and plan (create).
+rcdc_status build_pslot(Ing *g, PSlot &P, const Sizes &z) {
+    // the chunk-id kernel runs for up to ~60 ms (a 2 MiB chunk's
+    // SHA-256 chain on one lane): its stream gets the lowest priority, so
+    // HIP puts it on a hardware queue of its own class -- a stream that
+    // shared its queue waited behind it in order (r5o: each batch's
+    // chunking started only when the previous batch's ids were done)
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    NEW_TRY(hipStreamCreateWithPriority(&P.s_ids.h, hipStreamNonBlocking, prio_lo), "stream");
+    NEW_TRY(P.ev_ids.create(), "stream");
+    NEW_TRY(P.ev_sealed.create(), "stream");
+    NEW_TRY(P.ev_retired.create(), "stream");
+    // device buffers sized for a full batch up front (a hipFree inside
+    // the pipeline would synchronise the device): the slot's bytes, then
+    // the assembly region for streams' gathered pieces and carries
+    NEW_TRY(P.arena.alloc(g, z.arena, false), "arena");
+    NEW_TRY(P.staging.alloc(g, z.staging, false), "staging");
+    // the plan built once for a full-batch layout (allocations and
+    // synchronous uploads here, not inside the pipeline); each batch then
+    // re-lays it out on its compute stream, reusing the buffers
+    // (256 streams: its per-stream arrays then hold any batch of up to
+    // 256 files without a regrow; r5j logged five regrows per slot with
+    // a one-stream layout, each a device-wide hipFree)
+    constexpr uint32_t kPlanStreams = 256;
+    std::vector<uint64_t> off0(kPlanStreams), len0(kPlanStreams);
+    const uint64_t per = (g->batch_cap / kPlanStreams) & ~255ull;
+    for (uint32_t i = 0; i < kPlanStreams; i++) {
+        off0[i] = i * per;
+        len0[i] = per;
+    }
+    rcdc_plan *pl = nullptr;
+    if (rcdc_status ps = rcdc_plan_create(g->ctx, off0.data(), len0.data(), kPlanStreams,
+                                          g->batch_cap + 256, &pl))
+        return ps;
+    P.plan.reset(pl);
+    // ... and run once in that layout and in the one-stream layout (the
+    // walk path's buffers at full size; the arena's bytes do not matter):
+    // a plan's first run in a new layout allocated inside the pipeline,
+    // and each allocation's hipFree waited for every queued copy and
+    // kernel (r5u: 30-55 ms in each slot's first relayout)
+    std::vector<uint64_t> wc(g->batch_cap / 4096 + kPlanStreams + 16), wn(kPlanStreams);
+    for (uint32_t ns : {0u, 1u, 2u, 4u, 16u}) {  // as created, then walked layouts of 1-16 streams
+        std::vector<uint64_t> o(ns), l(ns);
+        const uint64_t each = (g->batch_cap / std::max(ns, 1u)) & ~255ull;
+        for (uint32_t i = 0; i < ns; i++) {
+            o[i] = i * each;
+            l[i] = each;
+        }
+        if (rcdc_status ps = ns ? rcdc::plan_relayout(pl, o.data(), l.data(), ns,
+                                                      g->batch_cap + 256, nullptr)
+                                : RCDC_OK)
+            return ps;
+        if (rcdc_status ps = rcdc_plan_run(pl, P.arena, nullptr)) return ps;
+        if (rcdc_status ps = rcdc_plan_results(pl, wc.data(), wc.size(), wn.data());
+            ps && ps != RCDC_ERR_CAPACITY)
+            return ps;
+    }
+    // short-chunk refs for a batch of minimum-size chunks
+    NEW_TRY(P.h_refs.alloc(g, z.refs_cap * 2, true), "refs");
+    NEW_TRY(P.d_refs.alloc(g, z.refs_cap * 2, false), "refs");
+    NEW_TRY(P.d_dig.alloc(g, z.refs_cap * 32, false), "refs");
+    return RCDC_OK;
+}
+
+// Every buffer, stream, event and plan of the engine, in this order (the
+// order of the allocations is part of the engine's timing: keep it).
+rcdc_status build_engine(Ing *g, const Sizes &z) {
+    for (uint32_t i = 0; i < g->nin; i++) {
+        g->in.push_back(std::make_unique<InSlot>());
+        NEW_TRY(g->in.back()->host.alloc(g, g->batch_cap, true), "input slot");
+        NEW_TRY(g->in.back()->h2d.create(), "event");
+    }
+    for (uint32_t i = 0; i < g->nout; i++) {
+        g->outs.push_back(std::make_unique<OutSlot>());
+        NEW_TRY(g->outs.back()->host.alloc(g, z.out_slot, true), "output slot");
+    }
+    // the open pack's carry buffers, sized for a default pack and its slack
+    for (int c = 0; c < 2; c++) NEW_TRY(g->carry[c].alloc(g, z.carry, false), "carry");
+    NEW_TRY(g->carry_pool.alloc(g, z.carry_pool, false), "stream carries");
+    g->ps = std::vector<PSlot>(g->depth);
+    for (auto &P : g->ps)
+        if (rcdc_status st = build_pslot(g, P, z)) return st;
+    NEW_TRY(g->frames.alloc(g, z.frames, false), "frames");
+    NEW_TRY(g->d_packs.alloc(g, z.frames, false), "packs");
+    NEW_TRY(hipStreamCreateWithFlags(&g->s_in.h, hipStreamNonBlocking), "streams");
+    NEW_TRY(hipStreamCreateWithFlags(&g->s_comp.h, hipStreamNonBlocking), "streams");
+    NEW_TRY(hipStreamCreateWithFlags(&g->s_out.h, hipStreamNonBlocking), "streams");
+    NEW_TRY(hipStreamCreateWithFlags(&g->s_back.h, hipStreamNonBlocking), "streams");
+    NEW_TRY(g->ev_comp.create(), "streams");
+    NEW_TRY(g->ev_back.create(), "streams");
+    NEW_TRY(g->ev_out.create(), "streams");
+    NEW_TRY(hipEventRecord(g->ev_out, g->s_out), "event");
+    return RCDC_OK;
+}
+#undef NEW_TRY
 
 }  // namespace
 
@@ -1961,8 +2100,6 @@ rcdc_status rcdc_ingest_create(rcdc_ctx *ctx, const rcdc_ingest_config *cfg,
     g->file_cb = file_cb;
     g->user = user;
     g->device = ctx_device(ctx);
-    g->prof = getenv("RCDC_INGEST_PROF") ? std::max(atoi(getenv("RCDC_INGEST_PROF")), 1) : 0;
-    if (const char *e = getenv("RCDC_INGEST_FAIL_ALLOC")) g->fail_alloc = (uint32_t)std::max(atoi(e), 0);
     g->level = cfg->zstd_level;
     g->compress = cfg->compress != 0;
     g->verify = cfg->extra_verify != 0;
@@ -1973,9 +2110,6 @@ rcdc_status rcdc_ingest_create(rcdc_ctx *ctx, const rcdc_ingest_config *cfg,
     const Sizes z = engine_sizes(ctx, cfg, g->sizer.pack_size());
     g->batch_cap = z.batch_cap;
     g->long_chunk = cfg->long_chunk ? cfg->long_chunk : (2ull << 20);
-    if (const char *e = getenv("RCDC_INGEST_KCOPY")) g->kcopy = (uint32_t)std::max(atoi(e), 0);
-    if (const char *e = getenv("RCDC_INGEST_COPY_PIECE"))
-        g->copy_piece = std::max<uint64_t>(strtoull(e, nullptr, 10), 1ull << 20);
     g->depth = z.depth;
     g->nin = z.nin;
     g->nout = z.nout;
@@ -1985,131 +2119,17 @@ rcdc_status rcdc_ingest_create(rcdc_ctx *ctx, const rcdc_ingest_config *cfg,
     g->asm_cap = z.asm_cap;
     g->pack_max_age = (cfg->pack_max_age_ms ? cfg->pack_max_age_ms : 300000) / 1e3;
     g->slot_max_age = (cfg->slot_max_age_ms ? cfg->slot_max_age_ms : 1000) / 1e3;
-    g->idx = new rcdc_index();
-    g->own_idx = true;
+    g->own_idx = std::make_unique<rcdc_index>();
+    g->idx = g->own_idx.get();
     for (uint32_t i = 0; i < z.max_streams; i++) g->free_cslots.push_back((int)(z.max_streams - 1 - i));
     Ing *gp = g.get();
     (void)hipSetDevice(g->device);
-    // any failure below: everything allocated so far is freed
-    auto fail_hip = [&](hipError_t e, const char *what) {
-        free_all(gp);
-        return set_error(RCDC_ERR_INTERNAL,
-                         (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-    };
-    auto fail_st = [&](rcdc_status st) {
+    if (rcdc_status st = build_engine(gp, z)) {
+        // what was built so far goes with the engine, the device still current
         const std::string m = rcdc_last_error();
-        free_all(gp);
+        g.reset();
         return set_error(st, m.c_str());
-    };
-    hipError_t e;
-    for (uint32_t i = 0; i < g->nin; i++) {
-        auto s = std::make_unique<InSlot>();
-        s->cap = g->batch_cap;
-        InSlot *sp = s.get();
-        g->in.push_back(std::move(s));
-        if ((e = ing_alloc(gp, &sp->host, sp->cap, true)) != hipSuccess) return fail_hip(e, "input slot");
-        if ((e = hipEventCreateWithFlags(&sp->h2d, hipEventDisableTiming)) != hipSuccess)
-            return fail_hip(e, "event");
     }
-    for (uint32_t i = 0; i < g->nout; i++) {
-        auto o = std::make_unique<OutSlot>();
-        o->cap = z.out_slot;
-        OutSlot *op = o.get();
-        g->outs.push_back(std::move(o));
-        if ((e = ing_alloc(gp, &op->host, op->cap, true)) != hipSuccess) return fail_hip(e, "output slot");
-    }
-    // the open pack's carry buffers, sized for a default pack and its slack
-    for (int c = 0; c < 2; c++) {
-        if ((e = ing_alloc(gp, &g->carry[c], z.carry, false)) != hipSuccess) return fail_hip(e, "carry");
-        g->carry_cap[c] = z.carry;
-    }
-    if ((e = ing_alloc(gp, &g->carry_pool, z.carry_pool, false)) != hipSuccess)
-        return fail_hip(e, "stream carries");
-    g->ps.resize(g->depth);
-    for (auto &P : g->ps) {
-        // the chunk-id kernel runs for up to ~60 ms (a 2 MiB chunk's
-        // SHA-256 chain on one lane): its stream gets the lowest priority, so
-        // HIP puts it on a hardware queue of its own class -- a stream that
-        // shared its queue waited behind it in order (r5o: each batch's
-        // chunking started only when the previous batch's ids were done)
-        int prio_lo = 0, prio_hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        if ((e = hipStreamCreateWithPriority(&P.s_ids, hipStreamNonBlocking, prio_lo)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&P.ev_ids, hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&P.ev_sealed, hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&P.ev_retired, hipEventDisableTiming)) != hipSuccess)
-            return fail_hip(e, "stream");
-        // device buffers sized for a full batch up front (a hipFree inside
-        // the pipeline would synchronise the device): the slot's bytes, then
-        // the assembly region for streams' gathered pieces and carries
-        if ((e = ing_alloc(gp, &P.arena, z.arena, false)) != hipSuccess) return fail_hip(e, "arena");
-        P.arena_cap = z.arena;
-        if ((e = ing_alloc(gp, &P.staging, z.staging, false)) != hipSuccess)
-            return fail_hip(e, "staging");
-        P.staging_cap = z.staging;
-        // the plan built once for a full-batch layout (allocations and
-        // synchronous uploads here, not inside the pipeline); each batch then
-        // re-lays it out on its compute stream, reusing the buffers
-        // (256 streams: its per-stream arrays then hold any batch of up to
-        // 256 files without a regrow; r5j logged five regrows per slot with
-        // a one-stream layout, each a device-wide hipFree)
-        constexpr uint32_t kPlanStreams = 256;
-        std::vector<uint64_t> off0(kPlanStreams), len0(kPlanStreams);
-        const uint64_t per = (g->batch_cap / kPlanStreams) & ~255ull;
-        for (uint32_t i = 0; i < kPlanStreams; i++) {
-            off0[i] = i * per;
-            len0[i] = per;
-        }
-        if (rcdc_status ps = rcdc_plan_create(ctx, off0.data(), len0.data(), kPlanStreams,
-                                              g->batch_cap + 256, &P.plan))
-            return fail_st(ps);
-        // ... and run once in that layout and in the one-stream layout (the
-        // walk path's buffers at full size; the arena's bytes do not matter):
-        // a plan's first run in a new layout allocated inside the pipeline,
-        // and each allocation's hipFree waited for every queued copy and
-        // kernel (r5u: 30-55 ms in each slot's first relayout)
-        {
-            std::vector<uint64_t> wc(g->batch_cap / 4096 + kPlanStreams + 16), wn(kPlanStreams);
-            if (rcdc_status ps = rcdc_plan_run(P.plan, P.arena, nullptr)) return fail_st(ps);
-            if (rcdc_status ps = rcdc_plan_results(P.plan, wc.data(), wc.size(), wn.data());
-                ps && ps != RCDC_ERR_CAPACITY)
-                return fail_st(ps);
-            for (uint32_t ns : {1u, 2u, 4u, 16u}) {  // walked layouts of 1-16 streams
-                std::vector<uint64_t> o(ns), l(ns);
-                const uint64_t each = (g->batch_cap / ns) & ~255ull;
-                for (uint32_t i = 0; i < ns; i++) {
-                    o[i] = i * each;
-                    l[i] = each;
-                }
-                if (rcdc_status ps = rcdc::plan_relayout(P.plan, o.data(), l.data(), ns,
-                                                         g->batch_cap + 256, nullptr))
-                    return fail_st(ps);
-                if (rcdc_status ps = rcdc_plan_run(P.plan, P.arena, nullptr)) return fail_st(ps);
-                if (rcdc_status ps = rcdc_plan_results(P.plan, wc.data(), wc.size(), wn.data());
-                    ps && ps != RCDC_ERR_CAPACITY)
-                    return fail_st(ps);
-            }
-        }
-        // short-chunk refs for a batch of minimum-size chunks
-        P.refs_cap = z.refs_cap;
-        if ((e = ing_alloc(gp, &P.h_refs, P.refs_cap * 16, true)) != hipSuccess ||
-            (e = ing_alloc(gp, &P.d_refs, P.refs_cap * 16, false)) != hipSuccess ||
-            (e = ing_alloc(gp, &P.d_dig, P.refs_cap * 32, false)) != hipSuccess)
-            return fail_hip(e, "refs");
-    }
-    if ((e = ing_alloc(gp, &g->frames, z.frames, false)) != hipSuccess) return fail_hip(e, "frames");
-    g->frames_cap = z.frames;
-    if ((e = ing_alloc(gp, &g->d_packs, z.frames, false)) != hipSuccess) return fail_hip(e, "packs");
-    g->d_packs_cap = z.frames;
-    if ((e = hipStreamCreateWithFlags(&g->s_in, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&g->s_comp, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&g->s_out, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&g->s_back, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&g->ev_comp, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&g->ev_back, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&g->ev_out, hipEventDisableTiming)) != hipSuccess)
-        return fail_hip(e, "streams");
-    if ((e = hipEventRecord(g->ev_out, g->s_out)) != hipSuccess) return fail_hip(e, "event");
     for (uint32_t i = 0; i < g->nthreads; i++) g->pool.emplace_back(pool_main, gp);
     g->waiter = std::thread(waiter_main, gp);
     g->worker = std::thread(worker_main, gp);
@@ -2123,12 +2143,7 @@ rcdc_status rcdc_ingest_add_index(rcdc_ingest *g, const uint8_t *ids, uint64_t n
     if (!g || (n && !ids)) return set_error(RCDC_ERR_INVALID_INPUT, "null argument");
     std::lock_guard<std::mutex> lk(g->mu);
     if (g->nbatches) return set_error(RCDC_ERR_INVALID_INPUT, "index ids after the first batch");
-    for (uint64_t i = 0; i < n; i++) {
-        Id32 id;
-        memcpy(id.b, ids + 32 * i, 32);
-        g->idx->insert(id);
-    }
-    return RCDC_OK;
+    return rcdc_index_add(g->idx, ids, n);
 }
 
 rcdc_status rcdc_ingest_reserve(rcdc_ingest *g, uint64_t len, uint8_t **buf, uint64_t *ticket) {
@@ -2253,7 +2268,7 @@ rcdc_status rcdc_ingest_finish(rcdc_ingest *g, rcdc_ingest_stats *stats) {
         g->cv_done.wait(lk, [&] { return g->packs_pending == 0 || g->err; });
         g->st.seconds = g->t_first ? now_s() - g->t_first : 0;
         if (stats) *stats = g->st;
-        if (g->prof) {
+        if (g->knobs.prof) {
             std::lock_guard<std::mutex> lk2(g->cb_mu);
             for (size_t b = 0; b < g->tl.size(); b++) {
                 fprintf(stderr, "ingest batch %zu:", b);
@@ -2296,8 +2311,7 @@ void rcdc_ingest_destroy(rcdc_ingest *g) {
         if (t.joinable()) t.join();
     (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();
-    free_all(g);
-    delete g;
+    delete g;  // its plans, buffers, events and streams go here, the device current
 }
 
 rcdc_status rcdc_index_create(rcdc_index **out) {
@@ -2331,9 +2345,8 @@ rcdc_status rcdc_ingest_set_index(rcdc_ingest *g, rcdc_index *idx) {
         std::lock_guard<std::mutex> l2(sh.mu);
         for (const Id32 &id : sh.set) idx->insert(id);
     }
-    if (g->own_idx) delete g->idx;
+    g->own_idx.reset();
     g->idx = idx;
-    g->own_idx = false;
     return RCDC_OK;
 }
 

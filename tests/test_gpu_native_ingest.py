@@ -249,3 +249,35 @@ def test_native_ingest_rejects(gpu_ctx):
             ing.add(3, b"x")
     finally:
         ing.close()
+
+
+def test_native_ingest_packs_close_where_the_packer_model_closes_them():
+    """The engine's packer against the Python model of the same rule
+    (pack.group_blobs_open: should_save, MAX_COUNT, take_data's add_size,
+    Packer::finalize): small chunks (4 / 16 / 64 KiB) and 8 MiB slots give
+    several batches with the open pack carried across each, and with
+    pack_size 1 MiB, grow factor 32 and current size 0 the limit moves with
+    every closed pack.  A 4 MiB file of zeros adds chunks the dedup drops.
+    The blobs per pack, in pack order, are the model's groups over all
+    packed blobs."""
+    from rustic_core_amd.chunker import Context
+    from rustic_core_amd.pack import PackSizer, group_blobs_open
+    params = (0x003DA3358B4DC173, 4 << 10, 16 << 10, 64 << 10)
+    ctx = Context.get(*params, device=0)
+    rng = np.random.default_rng(77)
+    files = [rng.integers(0, 256, n, dtype=np.uint8)
+             for n in (8 << 20, (8 << 20) - 3, (8 << 20) - 4099)]
+    files.append(np.zeros(4 << 20, np.uint8))
+    ing, stats = _run(ctx, files, batch_bytes=8 << 20, depth=2, pack_size=1 << 20,
+                      pack_grow_factor=32, pack_current_size=0)
+    try:
+        assert stats["batches"] >= 3
+        _check_all(files, ing, stats, 0, params=params)
+        blobs = [b for p in ing.packs for b in p["blobs"]]
+        sizer = PackSizer(1 << 20, 32, 0xFFFFFFFF, 0, 30, 300)
+        want, open_from = group_blobs_open([b[2] - 32 for b in blobs], sizer,
+                                           [b[3] for b in blobs], finalize=True)
+        assert open_from == len(blobs)
+        assert [len(p["blobs"]) for p in ing.packs] == [n for _, n in want]
+    finally:
+        ing.close()
