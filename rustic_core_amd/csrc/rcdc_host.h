@@ -1,6 +1,6 @@
 // rcdc_host.h -- what the host halves of the library share: the entry points
 // rcdc_runtime.cpp exports to the other units, the device guard, the error
-// helpers and the owning device buffer.  Host code only (rcdc_host_sha.cpp is
+// helpers and the owning buffers (DevBuf, PinnedBuf).  Host code only (rcdc_host_sha.cpp is
 // built without HIP and does not include it).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -109,6 +109,36 @@ public:
 
 private:
     T *p_ = nullptr;
+    uint64_t cap_ = 0;
+};
+
+// Page-locked host memory that only grows, owned like a DevBuf (the owner's
+// device is current and its streams are idle when it is freed).
+class PinnedBuf {
+public:
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() {
+        if (p_) (void)hipHostFree(p_);
+    }
+
+    uint8_t *get() const { return p_; }
+
+    // At least `need` bytes; the contents are lost when it grows, to `grown`
+    // bytes (the caller's headroom rule, >= need).
+    rcdc_status ensure(uint64_t need, uint64_t grown) {
+        if (need <= cap_) return RCDC_OK;
+        if (p_) HIP_TRY(hipHostFree(p_));
+        p_ = nullptr;
+        cap_ = 0;
+        HIP_TRY(hipHostMalloc((void **)&p_, grown, hipHostMallocDefault));
+        cap_ = grown;
+        return RCDC_OK;
+    }
+
+private:
+    uint8_t *p_ = nullptr;
     uint64_t cap_ = 0;
 };
 

@@ -1,5 +1,5 @@
 // rcdc_launch.h -- the launch and sizing functions of the kernel units, as
-// the host runtime (rcdc_runtime.cpp, rcdc_ingest.cpp) calls them.  Every
+// the host units (rcdc_runtime.cpp, the family units, rcdc_ingest.cpp) call them.  Every
 // defining .hip file includes this header too, so a signature that drifts is
 // a compile error in the defining unit, not a link error.
 #pragma once

@@ -1,5 +1,5 @@
-// rcdc_place_blobs: what the host half (rcdc_runtime.cpp) and the kernel
-// (rcdc_place.hip) share.  Included by those two units only.
+// rcdc_place_blobs: what the host half (rcdc_place.cpp, its tile planner in
+// rcdc_family_plans.h) and the kernel (rcdc_place.hip) share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,8 @@
-// rcdc_runtime.cpp -- host runtime behind include/rcdc.h.
+// rcdc_runtime.cpp -- host runtime behind include/rcdc.h: errors, the
+// context's create and destroy and what the family units share (rcdc_ctx.h),
+// plans, lanes, the host-buffer path, streams and the SHA-256 entry points.
+// The other kernel families have a unit each: rcdc_aead.cpp,
+// rcdc_zstd_host.cpp, rcdc_place.cpp, rcdc_dindex.cpp, rcdc_ixparse.cpp.
 //
 // Owns the device (tables, work lists, summaries, cut lists, pinned staging)
 // and maps the reference's chunker surface onto the two kernels:
@@ -27,10 +31,10 @@
 #include <vector>
 
 #include "../../include/rcdc.h"
+#include "rcdc_ctx.h"
 #include "rcdc_host.h"
 #include "rcdc_internal.h"
 #include "rcdc_launch.h"
-#include "rcdc_place.h"
 
 using namespace rcdc;
 
@@ -39,8 +43,9 @@ using namespace rcdc;
 // ---------------------------------------------------------------------------
 namespace {
 thread_local std::string g_err;
+}
 
-rcdc_status fail(rcdc_status st, const char *fmt, ...) {
+rcdc_status rcdc::fail(rcdc_status st, const char *fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -49,6 +54,8 @@ rcdc_status fail(rcdc_status st, const char *fmt, ...) {
     g_err = buf;
     return st;
 }
+
+namespace {
 
 // ---------------------------------------------------------------------------
 // GF(2) polynomial arithmetic for the Rabin64 tables (rustic_cdc Polynom64)
@@ -226,79 +233,6 @@ struct Lane {
     bool lay_cap = false;  // a capacity plan (one stream, length set per pass)
 };
 
-struct rcdc_ctx {
-    int device = 0;
-    uint64_t poly = 0, min = 0, avg = 0, max = 0;
-    int deg = 0;
-    int num_cus = 0;
-    int variant = kDefaultScanCode;  // scan-kernel configuration (RCDC_SCAN_VARIANT)
-    hipStream_t stream = nullptr;
-    uint64_t *d_tables = nullptr;
-    // host-buffer path: a pool of lanes (RCDC_LANES, default 16)
-    std::mutex pool_mu;
-    std::condition_variable pool_cv;
-    std::vector<Lane *> lanes, free_lanes;
-    uint32_t max_lanes = 16;
-    // blob encryption (rcdc_aead_*): calls on one context take turns
-    std::mutex aead_mu;
-    uint8_t aead_key[64] = {0};
-    bool aead_key_set = false;
-    DevBuf<AeadKeyDev> d_aead_key;
-    DevBuf<AeadBlob> d_aead_blobs;
-    DevBuf<AeadUnit> d_aead_units;
-    DevBuf<uint32_t> d_aead_unit0, d_aead_partials, d_aead_status;
-    DevBuf<uint8_t> d_aead_stage;  // pack headers
-    uint8_t *h_aead_up = nullptr;     // page-locked source of a call's uploads
-    uint64_t cap_aead_up = 0;
-    hipEvent_t aead_done = nullptr;
-    // ordering of calls on the context's stream (hip_stream == 0) with the
-    // legacy default stream (null_enter / null_leave)
-    hipEvent_t ev_null_in = nullptr, ev_null_out = nullptr;
-    // device tails of open streams (max + 256 bytes each): a pool, so opening
-    // and closing streams never calls hipMalloc / hipFree (which synchronise
-    // the device) once warm
-    std::mutex tail_mu;
-    std::vector<uint8_t *> tail_pool, tail_all;
-    // blob compression (rcdc_zstd_compress): calls on one context take turns
-    std::mutex zstd_mu;
-    DevBuf<ZstdTables> d_zstd_tabs;
-    DevBuf<ZstdBlob> d_zstd_blobs;
-    DevBuf<ZstdBlk> d_zstd_blks;
-    DevBuf<uint2> d_zstd_res;
-    DevBuf<uint64_t> d_zstd_bpos, d_zstd_lens, d_zstd_seq;
-    DevBuf<uint32_t> d_zstd_queue;  // per window: blocks taken past the first grid
-    DevBuf<uint8_t> d_zstd_slots;
-    DevBuf<uint32_t> d_zstd_far;  // far candidates: tables + maps per block (levels >= 3)
-    // frame checks (rcdc_zstd_check): calls on one context take turns
-    std::mutex zck_mu;
-    DevBuf<uint64_t> d_zck_refs;
-    DevBuf<uint32_t> d_zck_order, d_zck_status;
-    DevBuf<uint8_t> d_zck_scratch;
-    DevBuf<uint64_t> d_zck_blk0;  // block-parallel pass: per-frame block slots
-    DevBuf<uint8_t> d_zck_blks;
-    // frame decompression (rcdc_zstd_decompress): calls on one context take turns
-    std::mutex zdx_mu;
-    DevBuf<uint64_t> d_zdx_refs, d_zdx_lens;
-    DevBuf<ZdxFrame> d_zdx_frm;
-    DevBuf<ZdxPlace> d_zdx_place;
-    DevBuf<uint32_t> d_zdx_order, d_zdx_status;
-    DevBuf<uint8_t> d_zdx_ws;  // the workspace (ZdxLayout)
-    uint64_t zdx_stats[8] = {0};  // the last call's counters (rcdc_zstd_decompress_stats)
-    // pack files from sealed blobs (rcdc_pack_build_raw): copy units
-    DevBuf<uint64_t> d_copy_units;
-    // blobs placed into files (rcdc_place_blobs): calls on one context take turns
-    std::mutex place_mu;
-    DevBuf<PlaceTile> d_place_tiles;
-    DevBuf<uint64_t> d_place_dests;
-    DevBuf<uint32_t> d_place_nz;
-    uint8_t *h_place = nullptr;  // page-locked: destination addresses, read-back, tiles
-    uint64_t cap_h_place = 0;
-    // tile windows are uploaded on a stream of their own, so that window
-    // k + 1 arrives while window k runs; one event per window of a round
-    hipStream_t place_up = nullptr;
-    hipEvent_t place_ev[16] = {};
-};
-
 struct rcdc_stream {
     rcdc_ctx *ctx = nullptr;
     std::vector<uint8_t> pending;  // bytes from the current chunk start
@@ -314,7 +248,7 @@ struct rcdc_stream {
     hipEvent_t tail_ev = nullptr;  // the copy into d_tail (on the last pass's lane stream)
 };
 
-namespace {
+namespace rcdc {
 
 // hip_stream == 0 selects the context's own stream.  That stream is created
 // non-blocking, so on its own it is not ordered with the legacy default
@@ -385,6 +319,10 @@ hipError_t poll_stream(hipStream_t st) {
     if ((e = hipEventRecord(ev, st)) != hipSuccess) return e;
     return poll_event(ev);
 }
+
+}  // namespace rcdc
+
+namespace {
 
 // Choose the per-lane segment S (multiple of 128 in [512, 4096]): the scan
 // runs ceil(items / wave_slots) rounds of S + 64 slides per lane (64 = the
@@ -1400,8 +1338,6 @@ rcdc_status run_host_batch(rcdc_ctx *ctx, Lane *L, const rcdc_buf *bufs, uint32_
     return run_host_pieces(ctx, L, lens, pieces, cuts, cap, counts);
 }
 
-bool valid_ctx(const rcdc_ctx *c) { return c != nullptr; }
-
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1409,6 +1345,7 @@ bool valid_ctx(const rcdc_ctx *c) { return c != nullptr; }
 // otherwise a client of the C ABI below
 // ---------------------------------------------------------------------------
 namespace rcdc {
+bool valid_ctx(const rcdc_ctx *c) { return c != nullptr; }
 // Rebuild `pl` (created by rcdc_plan_create, its last run waited for) for a
 // new batch layout, reusing its device buffers; uploads on `up`.
 rcdc_status plan_relayout(rcdc_plan *pl, const uint64_t *offs, const uint64_t *lens, uint32_t n,
@@ -1554,17 +1491,11 @@ void rcdc_ctx_destroy(rcdc_ctx *c) {
         if (c->stream) (void)hipStreamSynchronize(c->stream);
         for (Lane *L : c->lanes) lane_free(c, L);
         (void)hipFree(c->d_tables);
-        (void)hipHostFree(c->h_aead_up);
-        if (c->aead_done) (void)hipEventDestroy(c->aead_done);
         if (c->ev_null_in) (void)hipEventDestroy(c->ev_null_in);
         if (c->ev_null_out) (void)hipEventDestroy(c->ev_null_out);
         for (uint8_t *t : c->tail_all) (void)hipFree(t);
-        (void)hipHostFree(c->h_place);
-        for (hipEvent_t e : c->place_ev)
-            if (e) (void)hipEventDestroy(e);
-        if (c->place_up) (void)hipStreamDestroy(c->place_up);
         if (c->stream) (void)hipStreamDestroy(c->stream);
-        delete c;  // its device buffers, with the device still current
+        delete c;  // what its members own, with the device still current
     }
 }
 
@@ -1919,1215 +1850,6 @@ rcdc_status rcdc_plan_device_digests(rcdc_plan *plan, uint64_t *d_digests) {
     *d_digests = (uint64_t)(uintptr_t)plan->d_dig.get();
     return RCDC_OK;
 }
-
-// ---- blob encryption (crypto/aespoly1305.rs:88-135 over HBM) ---------------
-
-}  // extern "C"
-
-namespace {
-
-// AES S-box from its definition (multiplicative inverse in GF(2^8), then the
-// affine map; FIPS-197 5.1.1), and the T-table / key schedules on the host.
-void aes_sbox(uint8_t sb[256]) {
-    uint8_t p = 1, q = 1;
-    do {
-        p = (uint8_t)(p ^ (p << 1) ^ ((p & 0x80) ? 0x1b : 0));  // p * 3
-        q ^= (uint8_t)(q << 1);                                  // q / 3
-        q ^= (uint8_t)(q << 2);
-        q ^= (uint8_t)(q << 4);
-        if (q & 0x80) q ^= 0x09;
-        const uint8_t x = (uint8_t)(q ^ (uint8_t)((q << 1) | (q >> 7)) ^
-                                    (uint8_t)((q << 2) | (q >> 6)) ^
-                                    (uint8_t)((q << 3) | (q >> 5)) ^ (uint8_t)((q << 4) | (q >> 4)));
-        sb[p] = x ^ 0x63;
-    } while (p != 1);
-    sb[0] = 0x63;
-}
-
-void aes_expand_host(const uint8_t *key, int nk, const uint8_t sb[256], uint32_t *rk) {
-    const int nr = nk + 6;
-    uint8_t rcon = 1;
-    for (int i = 0; i < nk; i++)
-        rk[i] = (uint32_t)key[4 * i] << 24 | (uint32_t)key[4 * i + 1] << 16 |
-                (uint32_t)key[4 * i + 2] << 8 | key[4 * i + 3];
-    auto sub = [&](uint32_t t) {
-        return (uint32_t)sb[t >> 24] << 24 | (uint32_t)sb[(t >> 16) & 255] << 16 |
-               (uint32_t)sb[(t >> 8) & 255] << 8 | sb[t & 255];
-    };
-    for (int i = nk; i < 4 * (nr + 1); i++) {
-        uint32_t t = rk[i - 1];
-        if (i % nk == 0) {
-            t = sub((t << 8) | (t >> 24)) ^ (uint32_t)rcon << 24;
-            rcon = (uint8_t)((rcon << 1) ^ ((rcon & 0x80) ? 0x1b : 0));
-        } else if (nk > 6 && i % nk == 4) {
-            t = sub(t);
-        }
-        rk[i] = rk[i - nk] ^ t;
-    }
-}
-
-// 2^130 - 5 arithmetic in 26-bit limbs (the device pmul, on the host)
-void p26_mul(const uint32_t a[5], const uint32_t b[5], uint32_t r[5]) {
-    const uint64_t b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3], b4 = b[4];
-    const uint64_t s1 = b1 * 5, s2 = b2 * 5, s3 = b3 * 5, s4 = b4 * 5;
-    const uint64_t a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4];
-    uint64_t d0 = a0 * b0 + a1 * s4 + a2 * s3 + a3 * s2 + a4 * s1;
-    uint64_t d1 = a0 * b1 + a1 * b0 + a2 * s4 + a3 * s3 + a4 * s2;
-    uint64_t d2 = a0 * b2 + a1 * b1 + a2 * b0 + a3 * s4 + a4 * s3;
-    uint64_t d3 = a0 * b3 + a1 * b2 + a2 * b1 + a3 * b0 + a4 * s4;
-    uint64_t d4 = a0 * b4 + a1 * b3 + a2 * b2 + a3 * b1 + a4 * b0;
-    d1 += d0 >> 26; d2 += d1 >> 26; d3 += d2 >> 26; d4 += d3 >> 26;
-    uint64_t h0 = (d0 & 0x3ffffff) + (d4 >> 26) * 5;
-    r[1] = (uint32_t)((d1 & 0x3ffffff) + (h0 >> 26));
-    r[0] = (uint32_t)(h0 & 0x3ffffff);
-    r[2] = (uint32_t)(d2 & 0x3ffffff);
-    r[3] = (uint32_t)(d3 & 0x3ffffff);
-    r[4] = (uint32_t)(d4 & 0x3ffffff);
-    // fully normalise (r[1] may carry)
-    const uint32_t c = r[1] >> 26;
-    r[1] &= 0x3ffffff;
-    r[2] += c;
-}
-
-void aead_key_material(const uint8_t key[64], AeadKeyDev *K) {
-    uint8_t sb[256];
-    aes_sbox(sb);
-    for (int x = 0; x < 256; x++) {
-        const uint8_t s1 = sb[x], s2 = (uint8_t)((s1 << 1) ^ ((s1 & 0x80) ? 0x1b : 0));
-        const uint8_t s3 = s2 ^ s1;
-        K->te[x] = (uint32_t)s2 << 24 | (uint32_t)s1 << 16 | (uint32_t)s1 << 8 | s3;
-    }
-    aes_expand_host(key, 8, sb, K->rk256);
-    aes_expand_host(key + 32, 4, sb, K->rk128);
-    uint8_t rb[16];
-    memcpy(rb, key + 48, 16);
-    rb[3] &= 15; rb[7] &= 15; rb[11] &= 15; rb[15] &= 15;
-    rb[4] &= 252; rb[8] &= 252; rb[12] &= 252;
-    uint64_t t0 = 0, t1 = 0;
-    for (int i = 7; i >= 0; i--) {
-        t0 = t0 << 8 | rb[i];
-        t1 = t1 << 8 | rb[8 + i];
-    }
-    const uint32_t r[5] = {(uint32_t)(t0 & 0x3ffffff), (uint32_t)((t0 >> 26) & 0x3ffffff),
-                           (uint32_t)(((t0 >> 52) | (t1 << 12)) & 0x3ffffff),
-                           (uint32_t)((t1 >> 14) & 0x3ffffff), (uint32_t)((t1 >> 40) & 0x3ffffff)};
-    const uint32_t one[5] = {1, 0, 0, 0, 0};
-    memcpy(K->rpow[0], one, sizeof one);
-    for (int i = 1; i <= 64; i++) p26_mul(K->rpow[i - 1], r, K->rpow[i]);
-    memcpy(K->r2j[0], r, sizeof r);
-    for (int j = 1; j < 32; j++) p26_mul(K->r2j[j - 1], K->r2j[j - 1], K->r2j[j]);
-}
-
-// A list of blobs over one input base, cut into units of kAeadUnitBlocks.
-struct AeadBatch {
-    const uint8_t *in = nullptr;
-    std::vector<AeadBlob> blobs;
-    std::vector<AeadUnit> units;
-    std::vector<uint32_t> unit0;  // per blob + 1 (closed by aead_launch)
-};
-
-rcdc_status aead_add(AeadBatch &B, const AeadBlob &b, uint32_t caller_index) {
-    const uint64_t nb = (b.len + 15) / 16;
-    if (nb >= (1ull << 32)) return fail(RCDC_ERR_UNSUPPORTED, "blob %u too large", caller_index);
-    const uint32_t bi = (uint32_t)B.blobs.size();
-    B.unit0.push_back((uint32_t)B.units.size());
-    B.blobs.push_back(b);
-    for (uint64_t b0 = 0; b0 < nb; b0 += kAeadUnitBlocks)
-        B.units.push_back({bi, (uint32_t)b0, (uint32_t)std::min<uint64_t>(nb, b0 + kAeadUnitBlocks), 0});
-    return RCDC_OK;
-}
-
-// Launch the batches (each its own input base) on one context scratch.
-// `staging` (optional) is copied to the scratch input buffer first and a
-// batch whose `in` is nullptr reads from it.  open: status per blob of the
-// batches in order (synchronous).  Calls on one context take turns.
-rcdc_status aead_launch(rcdc_ctx *ctx, bool open, const uint8_t key[64], std::vector<AeadBatch> &bt,
-                        uint8_t *out, hipStream_t st, const std::vector<uint8_t> *staging,
-                        std::vector<uint32_t> *status) {
-    std::lock_guard<std::mutex> lk(ctx->aead_mu);
-    DeviceGuard g(ctx->device);
-    // (the last call's work is done: every call ends synchronised)
-    if (!ctx->aead_done) HIP_TRY(hipEventCreateWithFlags(&ctx->aead_done, hipEventDisableTiming));
-    rcdc_status rs;
-    if ((rs = ctx->d_aead_key.ensure(1))) return rs;
-    if (!ctx->aead_key_set || memcmp(ctx->aead_key, key, 64) != 0) {
-        AeadKeyDev K;
-        aead_key_material(key, &K);
-        HIP_TRY(hipMemcpy(ctx->d_aead_key, &K, sizeof K, hipMemcpyHostToDevice));
-        memcpy(ctx->aead_key, key, 64);
-        ctx->aead_key_set = true;
-    }
-    uint64_t nb = 0, nu = 0;
-    for (AeadBatch &B : bt) {
-        B.unit0.push_back((uint32_t)B.units.size());
-        nb += B.blobs.size();
-        nu += B.units.size();
-    }
-    if ((rs = ctx->d_aead_blobs.ensure(nb))) return rs;
-    if ((rs = ctx->d_aead_units.ensure(nu))) return rs;
-    if ((rs = ctx->d_aead_unit0.ensure(nb + bt.size()))) return rs;
-    if ((rs = ctx->d_aead_partials.ensure(nu * 5))) return rs;
-    if ((rs = ctx->d_aead_status.ensure(nb))) return rs;
-    // the call's uploads go async on st from one page-locked buffer (free
-    // again: the last call's work is done, aead_done above).  Synchronous
-    // copies from pageable memory queued behind other streams' multi-GiB
-    // copies on the DMA engine (the ingest engine's batches) and stalled
-    // the calling thread for up to a whole copy.
-    auto r16 = [](uint64_t x) { return (x + 15) & ~15ull; };
-    uint64_t up = staging ? r16(staging->size()) : 0;
-    for (AeadBatch &B : bt)
-        up += r16(B.blobs.size() * sizeof(AeadBlob)) + r16(B.unit0.size() * 4) +
-              r16(B.units.size() * sizeof(AeadUnit));
-    if (up > ctx->cap_aead_up) {
-        if (ctx->h_aead_up) HIP_TRY(hipHostFree(ctx->h_aead_up));
-        ctx->h_aead_up = nullptr;
-        ctx->cap_aead_up = 0;
-        const uint64_t c = up + up / 2 + 4096;
-        HIP_TRY(hipHostMalloc((void **)&ctx->h_aead_up, c, hipHostMallocDefault));
-        ctx->cap_aead_up = c;
-    }
-    uint64_t hp = 0;
-    auto upload = [&](void *dst, const void *src, uint64_t n) -> hipError_t {
-        if (!n) return hipSuccess;
-        memcpy(ctx->h_aead_up + hp, src, n);
-        const hipError_t e = hipMemcpyAsync(dst, ctx->h_aead_up + hp, n, hipMemcpyHostToDevice, st);
-        hp += r16(n);
-        return e;
-    };
-    if (staging && !staging->empty()) {
-        if ((rs = ctx->d_aead_stage.ensure(staging->size() + 16)))
-            return rs;
-        HIP_TRY(upload(ctx->d_aead_stage, staging->data(), staging->size()));
-    }
-    uint64_t ob = 0, ou = 0, o0 = 0;
-    for (AeadBatch &B : bt) {
-        const uint32_t m = (uint32_t)B.blobs.size(), u = (uint32_t)B.units.size();
-        if (m) {
-            HIP_TRY(upload(ctx->d_aead_blobs + ob, B.blobs.data(), m * sizeof(AeadBlob)));
-            HIP_TRY(upload(ctx->d_aead_unit0 + o0, B.unit0.data(), (m + 1) * 4));
-        }
-        if (u) HIP_TRY(upload(ctx->d_aead_units + ou, B.units.data(), u * sizeof(AeadUnit)));
-        const uint8_t *in = B.in ? B.in : ctx->d_aead_stage;
-        HIP_TRY(launch_aead(open, in, out, ctx->d_aead_blobs + ob, m, ctx->d_aead_units + ou, u,
-                            ctx->d_aead_unit0 + o0, ctx->d_aead_key, ctx->d_aead_partials + ou * 5,
-                            ctx->d_aead_status + ob, (uint32_t)std::max(ctx->num_cus, 1), st));
-        ob += m;
-        ou += u;
-        o0 += m + 1;
-    }
-    // The call returns once its work is done: the context's scratch is then
-    // free for the next call with no event kept across calls.  (An event
-    // recorded on the caller's stream and synchronised in the next call
-    // failed once that stream had been destroyed in between, r5g; one
-    // recorded on the context's stream waited behind whatever long kernel
-    // shared that stream's hardware queue, r5l.)
-    HIP_TRY(hipEventRecord(ctx->aead_done, st));
-    HIP_TRY(poll_event(ctx->aead_done));
-    if (open && status) {
-        HIP_TRY(poll_event(ctx->aead_done));
-        status->assign(nb, 0);
-        if (nb) {  // on st (see plan_finish: not the legacy default stream)
-            HIP_TRY(hipMemcpyAsync(status->data(), ctx->d_aead_status, nb * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(poll_stream(st));
-        }
-    }
-    return RCDC_OK;
-}
-
-rcdc_status aead_run(rcdc_ctx *ctx, bool open, const uint8_t key[64], const void *d_in,
-                     const rcdc_aead_ref *refs, uint32_t n, void *d_out, uint32_t *status,
-                     void *hip_stream) {
-    if (!valid_ctx(ctx) || !key || (n && (!refs || !d_in || !d_out)) || (open && n && !status))
-        return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-    std::vector<AeadBatch> bt(1);
-    bt[0].in = (const uint8_t *)d_in;
-    std::vector<uint32_t> which;  // device blob -> caller index
-    rcdc_status rs;
-    for (uint32_t i = 0; i < n; i++) {
-        const rcdc_aead_ref &r = refs[i];
-        if (open && r.len < 32) {
-            // no room for nonce + tag: aespoly1305.rs:89-94 (< 16 bytes) and
-            // the AEAD's own length check (16..31) both fail before any MAC
-            status[i] = r.len < 16 ? 2u : 1u;
-            continue;
-        }
-        AeadBlob b{};
-        b.in_off = r.in_off;
-        b.len = open ? r.len - 32 : r.len;
-        b.out_off = r.out_off;
-        memcpy(b.nonce, r.nonce, 16);  // little-endian words of the nonce bytes
-        if ((rs = aead_add(bt[0], b, i))) return rs;
-        which.push_back(i);
-    }
-    std::vector<uint32_t> ds;
-    hipStream_t st;
-    {
-        DeviceGuard g(ctx->device);
-        if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
-        if ((rs = aead_launch(ctx, open, key, bt, (uint8_t *)d_out, st, nullptr,
-                              open ? &ds : nullptr)))
-            return rs;
-        if ((rs = null_leave(ctx, hip_stream, st))) return rs;
-    }
-    if (open)
-        for (size_t j = 0; j < which.size(); j++) status[which[j]] = ds[j];
-    return RCDC_OK;
-}
-
-static_assert(sizeof(rcdc_pack_blob) == 72, "rcdc_pack_blob is 72 B");
-static_assert(sizeof(rcdc_pack) == 48, "rcdc_pack is 48 B");
-
-// Pack files (blob/packer.rs:615-655, 693-735; repofile/packfile.rs): blobs
-// sealed back to back, then the sealed header (one HeaderEntry per blob:
-// type, u32 length, [u32 raw length], id) and its u32 length.
-// raw (add_raw): the blobs at in_off are sealed already (len = sealed bytes,
-// >= 32); they are copied into place and only the headers are sealed.
-// Device range copies (units of {src, dst, len, source base address}, at
-// most 1 MiB each) into d_out on st.  The unit list lives in the context
-// until the copy has run: calls take turns under the AEAD lock.
-rcdc_status copy_units_run(rcdc_ctx *ctx, const std::vector<uint64_t> &copies, void *d_out,
-                           hipStream_t st) {
-    if (copies.empty()) return RCDC_OK;
-    std::lock_guard<std::mutex> lk(ctx->aead_mu);
-    const uint64_t nu = copies.size() / 4;
-    rcdc_status rs;
-    if ((rs = ctx->d_copy_units.ensure(copies.size()))) return rs;
-    HIP_TRY(hipMemcpyAsync(ctx->d_copy_units, copies.data(), copies.size() * 8,
-                           hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_copy_ranges((uint8_t *)d_out, ctx->d_copy_units, (uint32_t)nu,
-                               (uint32_t)std::max(ctx->num_cus, 1), st));
-    // the host vector dies with the caller's call
-    HIP_TRY(poll_stream(st));
-    return RCDC_OK;
-}
-
-void push_copy(std::vector<uint64_t> &copies, const void *src_base, uint64_t src, uint64_t dst,
-               uint64_t len) {
-    for (uint64_t c = 0; c < len; c += 1u << 20) {
-        copies.push_back(src + c);
-        copies.push_back(dst + c);
-        copies.push_back(std::min<uint64_t>(1u << 20, len - c));
-        copies.push_back((uint64_t)(uintptr_t)src_base);
-    }
-}
-
-// srcs (raw only, n_src > 0): blob i's bytes are at srcs[blobs[i].pad] +
-// in_off (rcdc_pack_build_raw_multi); otherwise at d_in + in_off.
-rcdc_status pack_build(rcdc_ctx *ctx, const uint8_t key[64], const void *d_in,
-                       const rcdc_pack_blob *blobs, uint32_t nblobs, rcdc_pack *packs,
-                       uint32_t npacks, void *d_out, uint64_t out_len, uint32_t *blob_offsets,
-                       void *hip_stream, bool raw = false, const void *const *srcs = nullptr,
-                       uint32_t n_src = 0) {
-    if (n_src) {
-        if (!srcs) return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-        for (uint32_t j = 0; j < n_src; j++)
-            if (!srcs[j]) return fail(RCDC_ERR_INVALID_INPUT, "source %u is null", j);
-        d_in = srcs[0];
-    }
-    if (!valid_ctx(ctx) || !key || (npacks && (!packs || !d_out)) || (nblobs && (!blobs || !d_in)))
-        return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-    std::vector<AeadBatch> bt(2);
-    bt[0].in = (const uint8_t *)d_in;
-    bt[1].in = nullptr;  // headers: from the staging buffer
-    std::vector<uint8_t> hdr;
-    std::vector<uint64_t> copies;  // raw: (src, dst, len, 0) per unit of <= 1 MiB
-    rcdc_status rs;
-    for (uint32_t p = 0; p < npacks; p++) {
-        rcdc_pack &P = packs[p];
-        if (P.nblobs == 0 || (uint64_t)P.blob0 + P.nblobs > nblobs)
-            return fail(RCDC_ERR_INVALID_INPUT, "pack %u: blobs [%u, +%u) of %u", p, P.blob0,
-                        P.nblobs, nblobs);
-        uint64_t off = 0;
-        const size_t h0 = hdr.size();
-        for (uint32_t i = P.blob0; i < P.blob0 + P.nblobs; i++) {
-            const rcdc_pack_blob &b = blobs[i];
-            if (b.type > 1) return fail(RCDC_ERR_INVALID_INPUT, "blob %u: type %u", i, b.type);
-            if (raw && b.len < 32)
-                return fail(RCDC_ERR_INVALID_INPUT, "blob %u: %u sealed bytes (< 32)", i, b.len);
-            if (!raw && b.len > 0xFFFFFFFFu - 32u)
-                return fail(RCDC_ERR_UNSUPPORTED, "blob %u: %u bytes", i, b.len);
-            const uint32_t sealed = raw ? b.len : b.len + 32u;
-            if (blob_offsets) blob_offsets[i] = (uint32_t)off;
-            if (raw) {
-                if (n_src && b.pad >= n_src)
-                    return fail(RCDC_ERR_INVALID_INPUT, "blob %u: source %u of %u", i, b.pad, n_src);
-                push_copy(copies, n_src ? srcs[b.pad] : d_in, b.in_off, P.out_off + off, sealed);
-            } else {
-                AeadBlob a{};
-                a.in_off = b.in_off;
-                a.len = b.len;
-                a.out_off = P.out_off + off;
-                memcpy(a.nonce, b.nonce, 16);
-                if ((rs = aead_add(bt[0], a, i))) return rs;
-            }
-            // HeaderEntry (packfile.rs:88-124, little-endian)
-            hdr.push_back((uint8_t)(b.type + (b.uncompressed_len ? 2u : 0u)));
-            for (int j = 0; j < 4; j++) hdr.push_back((uint8_t)(sealed >> (8 * j)));
-            if (b.uncompressed_len)
-                for (int j = 0; j < 4; j++) hdr.push_back((uint8_t)(b.uncompressed_len >> (8 * j)));
-            hdr.insert(hdr.end(), b.id, b.id + 32);
-            off += sealed;
-        }
-        const uint64_t hlen = hdr.size() - h0;
-        P.header_len = (uint32_t)(hlen + 32);
-        P.size = off + hlen + 32 + 4;
-        if (P.size > 0xFFFFFFFFull)  // packer.rs:58 MAX_SIZE; offsets are u32
-            return fail(RCDC_ERR_UNSUPPORTED, "pack %u: %llu bytes", p, (unsigned long long)P.size);
-        if (P.out_off + P.size > out_len)
-            return fail(RCDC_ERR_INVALID_INPUT, "pack %u does not fit the output (%llu + %llu > %llu)",
-                        p, (unsigned long long)P.out_off, (unsigned long long)P.size,
-                        (unsigned long long)out_len);
-        AeadBlob h{};
-        h.in_off = h0;
-        h.len = hlen;
-        h.out_off = P.out_off + off;
-        memcpy(h.nonce, P.header_nonce, 16);
-        h.flags = kAeadAppendLen;
-        if ((rs = aead_add(bt[1], h, p))) return rs;
-    }
-    hdr.resize(hdr.size() + 4, 0);  // the kernel may read 3 bytes past a blob
-    DeviceGuard g(ctx->device);
-    hipStream_t st;
-    if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
-    if ((rs = copy_units_run(ctx, copies, d_out, st))) return rs;
-    if ((rs = aead_launch(ctx, false, key, bt, (uint8_t *)d_out, st, &hdr, nullptr))) return rs;
-    return null_leave(ctx, hip_stream, st);
-}
-
-// ---- blob compression (zstd frames, RFC 8878) --------------------------------
-
-// FSE_buildCTable of a normalized distribution (the format's symbol spread:
-// RFC 8878 4.1.1; zstd lib/compress/fse_compress.c): state table sorted by
-// symbol, and per symbol {deltaFindState, deltaNbBits}.
-void fse_build_ctable(const int16_t *norm, int nsym, int tlog, ZstdFseSym *tt, uint16_t *st) {
-    const int size = 1 << tlog, mask = size - 1, step = (size >> 1) + (size >> 3) + 3;
-    std::vector<int> sym(size), cumul(nsym + 1);
-    int high = size - 1;
-    for (int u = 1; u <= nsym; u++) {
-        if (norm[u - 1] == -1) {
-            cumul[u] = cumul[u - 1] + 1;
-            sym[high--] = u - 1;
-        } else {
-            cumul[u] = cumul[u - 1] + norm[u - 1];
-        }
-    }
-    int pos = 0;
-    for (int s = 0; s < nsym; s++)
-        for (int k = 0; k < norm[s]; k++) {
-            sym[pos] = s;
-            pos = (pos + step) & mask;
-            while (pos > high) pos = (pos + step) & mask;
-        }
-    for (int u = 0; u < size; u++) st[cumul[sym[u]]++] = (uint16_t)(size + u);
-    int total = 0;
-    for (int s = 0; s < nsym; s++) {
-        const int c = norm[s];
-        if (c == -1 || c == 1) {
-            tt[s].nbits = ((uint32_t)tlog << 16) - (uint32_t)size;
-            tt[s].find = total - 1;
-            total++;
-        } else if (c > 1) {
-            const int mbo = tlog - (31 - __builtin_clz((uint32_t)(c - 1)));
-            tt[s].nbits = ((uint32_t)mbo << 16) - ((uint32_t)c << mbo);
-            tt[s].find = total - c;
-            total += c;
-        } else {
-            tt[s].nbits = ((uint32_t)(tlog + 1) << 16) - (uint32_t)size;
-            tt[s].find = 0;
-        }
-    }
-}
-
-// The predefined distributions and code tables (RFC 8878 3.1.1.3.2.1-2).
-const ZstdTables &zstd_tables() {
-    static ZstdTables T;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        static const int16_t ll_norm[36] = {4, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 2, 2,
-                                            2, 2, 2, 2, 2, 2, 2, 3, 2, 1, 1, 1, 1, 1, -1, -1, -1, -1};
-        static const int16_t ml_norm[53] = {1, 4, 3, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1,
-                                            1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
-                                            1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1, -1, -1};
-        static const int16_t of_norm[29] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1,
-                                            1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1};
-        static const uint32_t ll_base[36] = {0,  1,  2,   3,   4,   5,   6,    7,    8,    9,
-                                             10, 11, 12,  13,  14,  15,  16,   18,   20,   22,
-                                             24, 28, 32,  40,  48,  64,  128,  256,  512,  1024,
-                                             2048, 4096, 8192, 16384, 32768, 65536};
-        static const uint8_t ll_bits[36] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1,
-                                            1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
-        static const uint32_t ml_base[53] = {
-            3,  4,  5,  6,  7,  8,  9,  10, 11,  12,  13,  14,   15,   16,   17,   18,   19, 20,
-            21, 22, 23, 24, 25, 26, 27, 28, 29,  30,  31,  32,   33,   34,   35,   37,   39, 41,
-            43, 47, 51, 59, 67, 83, 99, 131, 259, 515, 1027, 2051, 4099, 8195, 16387, 32771, 65539};
-        static const uint8_t ml_bits[53] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                            0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1,
-                                            2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
-        memset(&T, 0, sizeof T);
-        fse_build_ctable(ll_norm, 36, 6, T.ll, T.llst);
-        fse_build_ctable(ml_norm, 53, 6, T.ml, T.mlst);
-        fse_build_ctable(of_norm, 29, 5, T.of, T.ofst);
-        for (uint32_t v = 0; v < 64; v++) {
-            int c = 0;
-            while (c + 1 < 36 && ll_base[c + 1] <= v) c++;
-            T.llcode[v] = (uint8_t)c;
-        }
-        for (uint32_t v = 0; v < 128; v++) {
-            int c = 0;
-            while (c + 1 < 53 && ml_base[c + 1] - 3 <= v) c++;
-            T.mlcode[v] = (uint8_t)c;
-        }
-        memcpy(T.llbits, ll_bits, sizeof ll_bits);
-        memcpy(T.mlbits, ml_bits, sizeof ml_bits);
-    });
-    return T;
-}
-
-uint64_t zstd_blocks(uint64_t len) { return len ? (len + kZstdBlock - 1) / kZstdBlock : 1; }
-
-// Blocks per launch window: bounds the per-block scratch (32768 x 128 KiB);
-// windows run back to back on the stream, reusing it.
-constexpr uint64_t kZstdWindowBlocks = 32768;
-
-// RCDC_ZSTD_WINDOW_BLOCKS (tests): a smaller window, so a modest batch runs
-// the multi-window path (per-window queues, rebased indices, reused slots)
-static uint64_t zstd_window_blocks() {
-    if (const char *e = getenv("RCDC_ZSTD_WINDOW_BLOCKS")) {
-        const long long v = atoll(e);
-        if (v > 0) return std::min<uint64_t>((uint64_t)v, kZstdWindowBlocks);
-    }
-    return kZstdWindowBlocks;
-}
-
-rcdc_status zstd_compress(rcdc_ctx *ctx, int level, const void *d_in, const rcdc_zstd_ref *refs,
-                          uint32_t n, void *d_out, uint64_t *out_lens, void *hip_stream) {
-    if (!valid_ctx(ctx) || (n && (!refs || !d_in || !d_out || !out_lens)))
-        return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-    // zstd's accepted levels (ZSTD_minCLevel() .. ZSTD_maxCLevel(); decrypt.rs:20-24)
-    if (level < -(1 << 17) || level > 22)
-        return fail(RCDC_ERR_INVALID_INPUT, "zstd level %d outside [-131072, 22]", level);
-    for (uint32_t i = 0; i < n; i++)
-        if (refs[i].len > 0xFFFFFFFFull)  // decrypt.rs:479-487: data length must fit u32
-            return fail(RCDC_ERR_UNSUPPORTED, "blob %u: %llu bytes", i,
-                        (unsigned long long)refs[i].len);
-    if (!n) return RCDC_OK;
-    // descriptors of every window (block indices relative to the window,
-    // blob indices too), uploaded once
-    struct Win {
-        uint64_t blob0, nblob, blk0, nblk;
-    };
-    std::vector<ZstdBlob> blobs;
-    std::vector<ZstdBlk> blks;
-    std::vector<Win> wins;
-    uint64_t maxw = 0;
-    const uint64_t wblocks = zstd_window_blocks();
-    for (uint32_t i = 0; i < n;) {
-        Win w{blobs.size(), 0, blks.size(), 0};
-        while (i < n) {
-            const uint64_t nb = zstd_blocks(refs[i].len);
-            if (w.nblk && w.nblk + nb > wblocks) break;
-            ZstdBlob B{};
-            B.in_off = refs[i].in_off;
-            B.out_off = refs[i].out_off;
-            B.len = (uint32_t)refs[i].len;
-            B.blk0 = (uint32_t)w.nblk;
-            B.nblk = (uint32_t)nb;
-            for (uint64_t k = 0; k < nb; k++) {
-                ZstdBlk b{};
-                b.blob = (uint32_t)w.nblob;
-                b.start = (uint32_t)(k * kZstdBlock);
-                b.len = (uint32_t)std::min<uint64_t>(kZstdBlock, refs[i].len - k * kZstdBlock);
-                b.flags = (k == 0 ? 1u : 0u) | (k + 1 == nb ? 2u : 0u);
-                blks.push_back(b);
-            }
-            blobs.push_back(B);
-            w.nblk += nb;
-            w.nblob++;
-            i++;
-        }
-        maxw = std::max(maxw, w.nblk);
-        wins.push_back(w);
-    }
-    std::lock_guard<std::mutex> lk(ctx->zstd_mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st;
-    rcdc_status rs;
-    if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
-    if (!ctx->d_zstd_tabs) {
-        if ((rs = ctx->d_zstd_tabs.ensure(1))) return rs;
-        HIP_TRY(hipMemcpy(ctx->d_zstd_tabs, &zstd_tables(), sizeof(ZstdTables),
-                          hipMemcpyHostToDevice));
-    }
-    const uint32_t grid = zstd_block_grid((uint32_t)std::max(ctx->num_cus, 1), level);
-    // (+ 8 words: the last wave's 16-byte literal loads may pass its region by 20 bytes)
-    if ((rs = ctx->d_zstd_seq.ensure((uint64_t)grid * kZstdMaxSeq + 8)))
-        return rs;
-    const uint64_t nbl = blks.size(), nbo = blobs.size();
-    if ((rs = ctx->d_zstd_blobs.ensure(nbo))) return rs;
-    if ((rs = ctx->d_zstd_blks.ensure(nbl))) return rs;
-    if ((rs = ctx->d_zstd_res.ensure(nbl))) return rs;
-    if ((rs = ctx->d_zstd_bpos.ensure(nbl))) return rs;
-    if ((rs = ctx->d_zstd_lens.ensure(nbo))) return rs;
-    if ((rs = ctx->d_zstd_slots.ensure(maxw * kZstdSlot))) return rs;
-    const uint64_t farw = zstd_far_words(level, maxw);
-    if (farw && (rs = ctx->d_zstd_far.ensure(farw))) return rs;
-    // the block kernel's queue: 8 counters 64 B apart per window
-    if ((rs = ctx->d_zstd_queue.ensure(wins.size() * 128))) return rs;
-    HIP_TRY(hipMemsetAsync(ctx->d_zstd_queue, 0, wins.size() * 128 * 4, st));
-    HIP_TRY(hipMemcpyAsync(ctx->d_zstd_blobs, blobs.data(), nbo * sizeof(ZstdBlob),
-                           hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->d_zstd_blks, blks.data(), nbl * sizeof(ZstdBlk),
-                           hipMemcpyHostToDevice, st));
-    if (const char *e = getenv("RCDC_ZSTD_DBG"); e && (atoi(e) & 32)) {  // the buffers, to place a fault
-        auto rng = [](const char *nm, const void *p, uint64_t bytes) {
-            fprintf(stderr, "rcdc zstd buf %-6s [%p, %p) %llu B\n", nm, p, (const void *)((const char *)p + bytes),
-                    (unsigned long long)bytes);
-        };
-        rng("seq", ctx->d_zstd_seq, ctx->d_zstd_seq.capacity() * 8);
-        rng("slots", ctx->d_zstd_slots, ctx->d_zstd_slots.capacity());
-        rng("far", ctx->d_zstd_far, ctx->d_zstd_far.capacity() * 4);
-        rng("res", ctx->d_zstd_res, ctx->d_zstd_res.capacity() * 8);
-        rng("bpos", ctx->d_zstd_bpos, ctx->d_zstd_bpos.capacity() * 8);
-        rng("blobs", ctx->d_zstd_blobs, ctx->d_zstd_blobs.capacity() * sizeof(ZstdBlob));
-        rng("blks", ctx->d_zstd_blks, ctx->d_zstd_blks.capacity() * sizeof(ZstdBlk));
-        rng("tabs", ctx->d_zstd_tabs, ctx->d_zstd_tabs.capacity() * sizeof(ZstdTables));
-        rng("queue", ctx->d_zstd_queue, ctx->d_zstd_queue.capacity() * 4);
-        rng("in", d_in, 0);
-        rng("out", d_out, 0);
-        fprintf(stderr, "rcdc zstd grid %u nblk %llu maxw %llu level %d\n", grid, (unsigned long long)nbl,
-                (unsigned long long)maxw, level);
-    }
-    // RCDC_ZSTD_GUARD=1 (debugging): every scratch buffer of this call is a
-    // fresh allocation with 16 MiB of 0xCD before and after it, checked after
-    // the call; a kernel that strays past one is reported, not faulted
-    struct GBuf {
-        uint8_t *base = nullptr;
-        uint64_t bytes = 0;
-        const char *name = "";
-    };
-    std::vector<GBuf> gbufs;
-    static const bool zguard = getenv("RCDC_ZSTD_GUARD") != nullptr;
-    constexpr uint64_t kG = 16ull << 20;
-    auto galloc = [&](const char *nm, uint64_t bytes) -> uint8_t * {
-        GBuf b;
-        b.name = nm;
-        b.bytes = bytes;
-        if (hipMalloc((void **)&b.base, bytes + 2 * kG) != hipSuccess) return nullptr;
-        (void)hipMemset(b.base, 0xCD, bytes + 2 * kG);
-        gbufs.push_back(b);
-        return b.base + kG;
-    };
-    ZstdBlob *u_blobs = ctx->d_zstd_blobs;
-    ZstdBlk *u_blks = ctx->d_zstd_blks;
-    ZstdTables *u_tabs = ctx->d_zstd_tabs;
-    uint8_t *u_slots = ctx->d_zstd_slots;
-    uint64_t *u_seq = ctx->d_zstd_seq, *u_bpos = ctx->d_zstd_bpos, *u_lens = ctx->d_zstd_lens;
-    uint2 *u_res = ctx->d_zstd_res;
-    uint32_t *u_queue = ctx->d_zstd_queue, *u_far = farw ? ctx->d_zstd_far : nullptr;
-    if (zguard) {
-        HIP_TRY(hipStreamSynchronize(st));
-        u_blobs = (ZstdBlob *)galloc("blobs", nbo * sizeof(ZstdBlob));
-        u_blks = (ZstdBlk *)galloc("blks", nbl * sizeof(ZstdBlk));
-        u_tabs = (ZstdTables *)galloc("tabs", sizeof(ZstdTables));
-        u_slots = galloc("slots", maxw * kZstdSlot);
-        u_seq = (uint64_t *)galloc("seq", ((uint64_t)grid * kZstdMaxSeq + 8) * 8);
-        u_bpos = (uint64_t *)galloc("bpos", nbl * 8);
-        u_lens = (uint64_t *)galloc("lens", nbo * 8);
-        u_res = (uint2 *)galloc("res", nbl * 8);
-        u_queue = (uint32_t *)galloc("queue", wins.size() * 128 * 4);
-        if (farw) u_far = (uint32_t *)galloc("far", farw * 4);
-        for (const GBuf &gb : gbufs)
-            if (!gb.base) return fail(RCDC_ERR_INTERNAL, "zstd guard allocation");
-        HIP_TRY(hipMemcpy(u_blobs, blobs.data(), nbo * sizeof(ZstdBlob), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(u_blks, blks.data(), nbl * sizeof(ZstdBlk), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(u_tabs, &zstd_tables(), sizeof(ZstdTables), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(u_queue, 0, wins.size() * 128 * 4));
-        for (const GBuf &gb : gbufs)
-            fprintf(stderr, "rcdc zstd guarded %-6s [%p, %p)\n", gb.name, (void *)(gb.base + kG),
-                    (void *)(gb.base + kG + gb.bytes));
-    }
-    for (size_t k = 0; k < wins.size(); k++) {
-        const Win &w = wins[k];
-        HIP_TRY(launch_zstd((const uint8_t *)d_in, (uint8_t *)d_out, u_blobs + w.blob0,
-                            (uint32_t)w.nblob, u_blks + w.blk0, (uint32_t)w.nblk,
-                            u_tabs, u_slots, u_seq, grid, u_res + w.blk0, u_bpos + w.blk0,
-                            u_lens + w.blob0, u_queue + 128 * k, u_far, level, st));
-    }
-    if (zguard) {
-        HIP_TRY(hipStreamSynchronize(st));
-        std::vector<uint8_t> gh(kG);
-        for (const GBuf &gb : gbufs)
-            for (int side = 0; side < 2; side++) {
-                const uint8_t *gp = side ? gb.base + kG + gb.bytes : gb.base;
-                HIP_TRY(hipMemcpy(gh.data(), gp, kG, hipMemcpyDeviceToHost));
-                int64_t lo = -1, hi = -1;
-                for (uint64_t i = 0; i < kG; i++)
-                    if (gh[i] != 0xCD) {
-                        if (lo < 0) lo = (int64_t)i;
-                        hi = (int64_t)i;
-                    }
-                if (lo >= 0)
-                    fprintf(stderr, "rcdc zstd GUARD HIT %s %s: guard bytes %lld..%lld written\n", gb.name,
-                            side ? "after" : "before", (long long)lo, (long long)hi);
-            }
-        HIP_TRY(hipMemcpy(out_lens, u_lens, nbo * 8, hipMemcpyDeviceToHost));
-        for (const GBuf &gb : gbufs) (void)hipFree(gb.base);
-        return null_leave(ctx, hip_stream, st);
-    }
-    HIP_TRY(hipMemcpyAsync(out_lens, ctx->d_zstd_lens, nbo * 8, hipMemcpyDeviceToHost, st));
-    // the host descriptors die with this call
-    HIP_TRY(poll_stream(st));
-    if (const char *e = getenv("RCDC_ZSTD_DBG"))
-        if (atoi(e) & 4) zstd_prof_dump();
-    return null_leave(ctx, hip_stream, st);
-}
-
-// Frame checks.  Compressed frames: the block-parallel pass (a wave per
-// block at the position it has when the frame's blocks are 128 KiB), then
-// the frames it could not settle checked in order, a wave per frame, longest
-// first.  Stored bytes: a wave per blob.
-rcdc_status zstd_check(rcdc_ctx *ctx, const void *d_frames, const void *d_data,
-                       const rcdc_zstd_check_ref *refs, uint32_t n, uint32_t flags,
-                       uint32_t *status, void *hip_stream) {
-    if (!valid_ctx(ctx) || (n && (!refs || !d_frames || !d_data || !status)))
-        return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-    if (!n) return RCDC_OK;
-    const bool stored = (flags & RCDC_CHECK_STORED) != 0;
-    static const bool blockpar = !(getenv("RCDC_CHECK_BLOCKS") && atoi(getenv("RCDC_CHECK_BLOCKS")) == 0);
-    std::lock_guard<std::mutex> lk(ctx->zck_mu);
-    DeviceGuard g(ctx->device);
-    hipStream_t st;
-    rcdc_status rs;
-    if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
-    // resident waves per CU (12 or 16, by the registers' budget)
-    const uint32_t grid = (uint32_t)std::max(ctx->num_cus, 1) * zstd_check_waves_per_cu();
-    if ((rs = ctx->d_zck_refs.ensure(4ull * n))) return rs;
-    if ((rs = ctx->d_zck_order.ensure((uint64_t)n + 16))) return rs;
-    if ((rs = ctx->d_zck_status.ensure(n))) return rs;
-    if ((rs = ctx->d_zck_scratch.ensure(zstd_check_scratch_bytes(grid))))
-        return rs;
-    uint32_t *ctr = ctx->d_zck_order + n;  // the queue counter sits after the order array
-    HIP_TRY(hipMemcpyAsync(ctx->d_zck_refs, refs, sizeof(rcdc_zstd_check_ref) * n,
-                           hipMemcpyHostToDevice, st));
-    std::vector<uint32_t> order;
-    if (!stored && blockpar) {
-        std::vector<uint64_t> blk0(n + 1, 0);
-        for (uint32_t i = 0; i < n; i++)
-            blk0[i + 1] = blk0[i] + std::max<uint64_t>((refs[i].data_len + kZstdBlock - 1) / kZstdBlock, 1);
-        const uint64_t nblk = blk0[n];
-        if ((rs = ctx->d_zck_blk0.ensure(n + 1ull))) return rs;
-        if ((rs = ctx->d_zck_blks.ensure(nblk * zstd_blkdesc_bytes())))
-            return rs;
-        HIP_TRY(hipMemcpyAsync(ctx->d_zck_blk0, blk0.data(), 8ull * (n + 1), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(ctr, 0, 4, st));
-        HIP_TRY(launch_zstd_check_blocks((const uint8_t *)d_frames, (const uint8_t *)d_data,
-                                         ctx->d_zck_refs, ctx->d_zck_blk0, n, ctx->d_zck_blks, nblk,
-                                         ctx->d_zck_scratch, grid, ctx->d_zck_status, ctr, st));
-        HIP_TRY(hipMemcpyAsync(status, ctx->d_zck_status, 4ull * n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(poll_stream(st));
-        for (uint32_t i = 0; i < n; i++)
-            if (status[i] == 3u) order.push_back(i);
-    } else {
-        order.resize(n);
-        for (uint32_t i = 0; i < n; i++) order[i] = i;
-    }
-    if (!order.empty()) {
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-            return refs[a].frame_len > refs[b].frame_len;
-        });
-        HIP_TRY(hipMemsetAsync(ctr, 0, 4, st));
-        HIP_TRY(hipMemcpyAsync(ctx->d_zck_order, order.data(), 4ull * order.size(),
-                               hipMemcpyHostToDevice, st));
-        HIP_TRY(launch_zstd_check((const uint8_t *)d_frames, (const uint8_t *)d_data, ctx->d_zck_refs,
-                                  ctx->d_zck_order, (uint32_t)order.size(), stored,
-                                  ctx->d_zck_scratch, grid, ctx->d_zck_status, ctr, st));
-        HIP_TRY(hipMemcpyAsync(status, ctx->d_zck_status, 4ull * n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(poll_stream(st));
-    }
-    if (const char *e = getenv("RCDC_ZSTD_DBG"))
-        if (atoi(e) & 8) zstd_check_prof_dump();
-    return null_leave(ctx, hip_stream, st);
-}
-
-// The decompressor's workspace for nblk blocks and `data` bytes of literals
-// and sequence records: the one place its regions are laid out.
-ZdxLayout zdx_layout(uint64_t nblk, uint64_t data) {
-    auto up = [](uint64_t v) { return (v + 255) & ~255ull; };
-    ZdxLayout l;
-    l.blk_off = 0;
-    l.blk_cap = nblk * sizeof(ZdxBlk);
-    l.res_off = up(l.blk_off + l.blk_cap);
-    l.res_cap = nblk * sizeof(ZdxRes);
-    l.data_off = up(l.res_off + l.res_cap);
-    l.data_cap = data;
-    l.total = up(l.data_off + l.data_cap);
-    return l;
-}
-
-// Frame decompression: the header walk (counting), the workspace laid out
-// from what it found, then per group of whole frames the header walk again
-// (writing block descriptors), the parallel entropy stage, the in-order
-// entropy pass for the flagged frames, and the copy stage.
-rcdc_status zstd_decompress(rcdc_ctx *ctx, const void *d_frames, const rcdc_zstd_dec_ref *refs,
-                            uint32_t n, uint32_t flags, void *d_out, uint64_t *out_lens,
-                            uint32_t *status, void *hip_stream) {
-    if (!valid_ctx(ctx) || (n && (!refs || !d_frames || !d_out || !out_lens || !status)))
-        return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-    if (flags) return fail(RCDC_ERR_INVALID_INPUT, "rcdc_zstd_decompress: unknown flags");
-    // the data region's cap (the one rcdc_zstd_compress documents for its slots)
-    static const uint64_t ws_max = getenv("RCDC_ZDX_WS_MAX")
-                                       ? std::max<uint64_t>(strtoull(getenv("RCDC_ZDX_WS_MAX"), nullptr, 10), 1)
-                                       : 4ull << 30;
-    static const bool blockpar = !(getenv("RCDC_ZDX_BLOCKS") && atoi(getenv("RCDC_ZDX_BLOCKS")) == 0);
-    std::lock_guard<std::mutex> lk(ctx->zdx_mu);
-    memset(ctx->zdx_stats, 0, sizeof ctx->zdx_stats);
-    if (!n) return RCDC_OK;
-    DeviceGuard g(ctx->device);
-    hipStream_t st;
-    rcdc_status rs;
-    if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
-    const uint32_t grid = (uint32_t)std::max(ctx->num_cus, 1) * zdx_waves_per_cu();
-    if ((rs = ctx->d_zdx_refs.ensure(4ull * n))) return rs;
-    if ((rs = ctx->d_zdx_lens.ensure(n))) return rs;
-    if ((rs = ctx->d_zdx_frm.ensure(n))) return rs;
-    if ((rs = ctx->d_zdx_place.ensure(n))) return rs;
-    if ((rs = ctx->d_zdx_order.ensure(2ull * n + 16))) return rs;
-    if ((rs = ctx->d_zdx_status.ensure(n))) return rs;
-    const uint8_t *frames = (const uint8_t *)d_frames;
-    HIP_TRY(hipMemcpyAsync(ctx->d_zdx_refs, refs, sizeof(rcdc_zstd_dec_ref) * n, hipMemcpyHostToDevice, st));
-    // 1. count: blocks and workspace bytes per frame
-    const ZdxLayout none = zdx_layout(0, 0);
-    HIP_TRY(launch_zdx_blocks(frames, ctx->d_zdx_refs, n, false, !blockpar, nullptr, none, nullptr,
-                              ctx->d_zdx_frm, st));
-    std::vector<ZdxFrame> hf(n);
-    HIP_TRY(hipMemcpyAsync(hf.data(), ctx->d_zdx_frm, sizeof(ZdxFrame) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(poll_stream(st));
-    // 2. groups of whole frames within the cap (a frame above it: a group of its own)
-    struct Group {
-        uint32_t a, b;
-        uint64_t nblk, data;
-    };
-    std::vector<Group> groups;
-    std::vector<ZdxPlace> place(n);
-    uint64_t peak = 0;
-    for (uint32_t i = 0; i < n;) {
-        Group G{i, i, 0, 0};
-        while (G.b < n) {
-            const ZdxFrame &F = hf[G.b];
-            const uint64_t need = F.status ? 0 : F.need;
-            if (G.b > G.a && (G.data + need > ws_max || G.nblk + F.nblk > (1ull << 31))) break;
-            place[G.b].blk0 = G.nblk;  // (every block the walk reaches has a slot,
-            place[G.b].data0 = G.data;  //  also in a frame it then refuses)
-            G.nblk += F.nblk;
-            G.data += need;
-            G.b++;
-        }
-        peak = std::max(peak, zdx_layout(G.nblk, G.data).total);
-        groups.push_back(G);
-        i = G.b;
-    }
-    if ((rs = ctx->d_zdx_ws.ensure(peak))) return rs;
-    HIP_TRY(hipMemcpyAsync(ctx->d_zdx_place, place.data(), sizeof(ZdxPlace) * n, hipMemcpyHostToDevice, st));
-    uint32_t *d_list = ctx->d_zdx_order, *d_ord = ctx->d_zdx_order + n, *ctr = ctx->d_zdx_order + 2ull * n;
-    std::vector<uint32_t> list, order;
-    // RCDC_ZDX_TIME: HIP-event times of the entropy kernels and of the copy
-    // kernel into the counters (tools/zstd_prof.py); a sync per group
-    static const bool timed = getenv("RCDC_ZDX_TIME") && atoi(getenv("RCDC_ZDX_TIME"));
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (timed)
-        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
-    // 3. per group: descriptors, entropy (parallel, then in order), copy.
-    // Indices inside a group count from its first frame.
-    for (const Group &G : groups) {
-        const uint32_t m = G.b - G.a;
-        const ZdxLayout lay = zdx_layout(G.nblk, G.data);
-        list.clear();
-        order.resize(m);
-        for (uint32_t j = 0; j < m; j++) {
-            order[j] = j;
-            const ZdxFrame &F = hf[G.a + j];
-            if (F.status) continue;
-            if (F.flags & kZdxInOrder) {
-                list.push_back(j);
-                ctx->zdx_stats[2] += F.ncomp;
-            } else {
-                ctx->zdx_stats[1] += F.ncomp;
-                ctx->zdx_stats[3] += F.ntreeless;
-            }
-        }
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-            return refs[G.a + x].frame_len > refs[G.a + y].frame_len;
-        });
-        const uint64_t *grefs = ctx->d_zdx_refs + 4ull * G.a;
-        ZdxFrame *gfrm = ctx->d_zdx_frm + G.a;
-        const ZdxPlace *gplace = ctx->d_zdx_place + G.a;
-        HIP_TRY(hipMemsetAsync(ctr, 0, 16, st));
-        if (!list.empty())
-            HIP_TRY(hipMemcpyAsync(d_list, list.data(), 4ull * list.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_ord, order.data(), 4ull * m, hipMemcpyHostToDevice, st));
-        HIP_TRY(launch_zdx_blocks(frames, grefs, m, true, !blockpar, gplace, lay, ctx->d_zdx_ws, gfrm, st));
-        if (timed) HIP_TRY(hipEventRecord(ev[0], st));
-        if (blockpar)
-            HIP_TRY(launch_zdx_entropy(frames, gfrm, lay, ctx->d_zdx_ws, G.nblk, grid, ctr, st));
-        HIP_TRY(launch_zdx_inorder(frames, gfrm, gplace, d_list, (uint32_t)list.size(), lay,
-                                   ctx->d_zdx_ws, grid, ctr + 1, st));
-        if (timed) HIP_TRY(hipEventRecord(ev[1], st));
-        HIP_TRY(launch_zdx_copy(frames, grefs, gfrm, gplace, d_ord, m, lay, ctx->d_zdx_ws,
-                                (uint8_t *)d_out, ctx->d_zdx_lens + G.a, ctx->d_zdx_status + G.a, grid,
-                                ctr + 2, st));
-        if (timed) HIP_TRY(hipEventRecord(ev[2], st));
-        // the next group's uploads reuse list / order: this group's are read
-        if (groups.size() > 1 || timed) HIP_TRY(poll_stream(st));
-        if (timed) {
-            float a = 0, c = 0;
-            HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-            HIP_TRY(hipEventElapsedTime(&c, ev[1], ev[2]));
-            ctx->zdx_stats[6] += (uint64_t)(a * 1e3f);
-            ctx->zdx_stats[7] += (uint64_t)(c * 1e3f);
-        }
-    }
-    if (timed)
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    HIP_TRY(hipMemcpyAsync(status, ctx->d_zdx_status, 4ull * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_lens, ctx->d_zdx_lens, 8ull * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(poll_stream(st));
-    ctx->zdx_stats[0] = n;
-    ctx->zdx_stats[4] = groups.size();
-    ctx->zdx_stats[5] = peak;
-    return null_leave(ctx, hip_stream, st);
-}
-
-// The header walk on the host: the first frame of `frame`.
-rcdc_status zstd_frame_info(const uint8_t *f, uint64_t len, uint64_t *content_size,
-                            uint64_t *out_bound, uint32_t *nblocks) {
-    if (!f || !content_size || !out_bound || !nblocks)
-        return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-    if (len < 6 || f[0] != 0x28 || f[1] != 0xB5 || f[2] != 0x2F || f[3] != 0xFD)
-        return fail(RCDC_ERR_INVALID_INPUT, "not a zstd frame");
-    const uint32_t fhd = f[4];
-    if (fhd & 8u) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: reserved bit set");
-    const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1u, cksum = (fhd >> 2) & 1u,
-                   did_flag = fhd & 3u;
-    uint64_t q = 5 + (single ? 0 : 1);
-    const uint32_t did_len = did_flag == 0 ? 0 : did_flag == 1 ? 1 : did_flag == 2 ? 2 : 4;
-    const uint32_t fcs_len = fcs_flag == 0 ? (single ? 1 : 0) : fcs_flag == 1 ? 2 : fcs_flag == 2 ? 4 : 8;
-    if (q + did_len + fcs_len > len) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: header cut off");
-    uint32_t did = 0;
-    for (uint32_t j = 0; j < did_len; j++) did |= (uint32_t)f[q + j] << (8 * j);
-    if (did) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: dictionaries are not supported");
-    q += did_len;
-    uint64_t fcs = 0;
-    for (uint32_t j = 0; j < fcs_len; j++) fcs |= (uint64_t)f[q + j] << (8 * j);
-    if (fcs_len == 2) fcs += 256;
-    q += fcs_len;
-    uint64_t bound = 0;
-    uint32_t nb = 0;
-    for (;;) {
-        if (q + 3 > len) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: block header past the end");
-        const uint32_t bh = f[q] | (f[q + 1] << 8) | ((uint32_t)f[q + 2] << 16);
-        q += 3;
-        const uint32_t last = bh & 1u, btype = (bh >> 1) & 3u, bsize = bh >> 3;
-        const uint64_t csz = btype == 1 ? 1u : bsize;
-        if (btype == 3) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: reserved block type");
-        if (q + csz > len) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: block past the end");
-        bound += btype == 2 ? (bsize ? kZstdBlock : 0u) : bsize;
-        q += csz;
-        nb++;
-        if (last) break;
-    }
-    if (cksum && q + 4 > len) return fail(RCDC_ERR_INVALID_INPUT, "zstd frame: checksum cut off");
-    *content_size = fcs_len ? fcs : UINT64_MAX;
-    *out_bound = bound;
-    *nblocks = nb;
-    return RCDC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-rcdc_status rcdc_zstd_decompress(rcdc_ctx *ctx, const void *d_frames, const rcdc_zstd_dec_ref *refs,
-                                 uint32_t n, uint32_t flags, void *d_out, uint64_t *out_lens,
-                                 uint32_t *status, void *hip_stream) {
-    return zstd_decompress(ctx, d_frames, refs, n, flags, d_out, out_lens, status, hip_stream);
-}
-
-rcdc_status rcdc_zstd_frame_info(const uint8_t *frame, uint64_t len, uint64_t *content_size,
-                                 uint64_t *out_bound, uint32_t *nblocks) {
-    return zstd_frame_info(frame, len, content_size, out_bound, nblocks);
-}
-
-rcdc_status rcdc_zstd_decompress_stats(rcdc_ctx *ctx, uint64_t out[8]) {
-    if (!valid_ctx(ctx) || !out) return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-    std::lock_guard<std::mutex> lk(ctx->zdx_mu);
-    memcpy(out, ctx->zdx_stats, sizeof ctx->zdx_stats);
-    return RCDC_OK;
-}
-
-rcdc_status rcdc_zstd_check(rcdc_ctx *ctx, const void *d_frames, const void *d_data,
-                            const rcdc_zstd_check_ref *refs, uint32_t n, uint32_t flags,
-                            uint32_t *status, void *hip_stream) {
-    return zstd_check(ctx, d_frames, d_data, refs, n, flags, status, hip_stream);
-}
-
-rcdc_status rcdc_aead_seal(rcdc_ctx *ctx, const uint8_t *key, const void *d_in,
-                           const rcdc_aead_ref *refs, uint32_t n, void *d_out, void *hip_stream) {
-    return aead_run(ctx, false, key, d_in, refs, n, d_out, nullptr, hip_stream);
-}
-
-rcdc_status rcdc_aead_open(rcdc_ctx *ctx, const uint8_t *key, const void *d_in,
-                           const rcdc_aead_ref *refs, uint32_t n, void *d_out, uint32_t *status,
-                           void *hip_stream) {
-    return aead_run(ctx, true, key, d_in, refs, n, d_out, status, hip_stream);
-}
-
-rcdc_status rcdc_pack_build(rcdc_ctx *ctx, const uint8_t *key, const void *d_in,
-                            const rcdc_pack_blob *blobs, uint32_t nblobs, rcdc_pack *packs,
-                            uint32_t npacks, void *d_out, uint64_t out_len,
-                            uint32_t *blob_offsets, void *hip_stream) {
-    return pack_build(ctx, key, d_in, blobs, nblobs, packs, npacks, d_out, out_len, blob_offsets,
-                      hip_stream);
-}
-
-rcdc_status rcdc_pack_build_raw(rcdc_ctx *ctx, const uint8_t *key, const void *d_in,
-                                const rcdc_pack_blob *blobs, uint32_t nblobs, rcdc_pack *packs,
-                                uint32_t npacks, void *d_out, uint64_t out_len,
-                                uint32_t *blob_offsets, void *hip_stream) {
-    return pack_build(ctx, key, d_in, blobs, nblobs, packs, npacks, d_out, out_len, blob_offsets,
-                      hip_stream, true);
-}
-
-rcdc_status rcdc_pack_build_raw_multi(rcdc_ctx *ctx, const uint8_t *key,
-                                      const void *const *d_ins, uint32_t n_ins,
-                                      const rcdc_pack_blob *blobs, uint32_t nblobs,
-                                      rcdc_pack *packs, uint32_t npacks, void *d_out,
-                                      uint64_t out_len, uint32_t *blob_offsets, void *hip_stream) {
-    if (n_ins == 0) return fail(RCDC_ERR_INVALID_INPUT, "no input buffers");
-    return pack_build(ctx, key, nullptr, blobs, nblobs, packs, npacks, d_out, out_len,
-                      blob_offsets, hip_stream, true, d_ins, n_ins);
-}
-
-rcdc_status rcdc_copy_ranges(rcdc_ctx *ctx, const void *const *d_ins, uint32_t n_ins,
-                             const rcdc_copy_ref *refs, uint32_t n, void *d_out,
-                             void *hip_stream) {
-    if (!valid_ctx(ctx) || (n && (!refs || !d_out || !d_ins || !n_ins)))
-        return fail(RCDC_ERR_INVALID_INPUT, "null argument");
-    std::vector<uint64_t> copies;
-    copies.reserve(4 * (size_t)n);
-    for (uint32_t i = 0; i < n; i++) {
-        const rcdc_copy_ref &c = refs[i];
-        if (c.src >= n_ins || !d_ins[c.src])
-            return fail(RCDC_ERR_INVALID_INPUT, "copy %u: source %u of %u", i, c.src, n_ins);
-        push_copy(copies, d_ins[c.src], c.in_off, c.out_off, c.len);
-    }
-    DeviceGuard g(ctx->device);
-    hipStream_t st;
-    rcdc_status rs;
-    if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
-    if ((rs = copy_units_run(ctx, copies, d_out, st))) return rs;
-    return null_leave(ctx, hip_stream, st);
-}
-
-static_assert(sizeof(rcdc_place_blob) == 32, "rcdc_place_blob is 32 B");
-static_assert(sizeof(rcdc_place_dest) == 16, "rcdc_place_dest is 16 B");
-
-// Tiles a call keeps at once, in page-locked memory and on the device (32 MiB
-// of descriptors, 64 GiB of source).  A call with more runs in rounds: the
-// stream is drained and the buffers are filled again.  RCDC_PLACE_TILES:
-// another cap (the tests' rounds).
-static uint64_t place_tile_cap() {
-    uint64_t cap = 1u << 20;
-    if (const char *e = getenv("RCDC_PLACE_TILES")) cap = (uint64_t)atoll(e);
-    return std::min<uint64_t>(std::max<uint64_t>(cap, 1), 1u << 20);
-}
-
-// Decoded blobs to their file positions (restore.rs:630-668).  Everything is
-// validated before the first launch; then the tile list (rcdc_place.h) is
-// built blob by blob in page-locked memory and launched in windows that grow
-// from 4096 tiles, doubling: the first launch goes out early, later ones are
-// few, and the host builds window k + 1 while window k runs.
-rcdc_status rcdc_place_blobs(rcdc_ctx *ctx, const void *const *d_ins, const uint64_t *in_lens,
-                             uint32_t n_ins, const rcdc_place_blob *blobs, uint32_t nblobs,
-                             const rcdc_place_dest *dests, uint32_t ndests_total,
-                             void *const *d_outs, const uint64_t *out_lens, uint32_t n_outs,
-                             uint32_t flags, uint8_t *zero, void *hip_stream) {
-    if (!valid_ctx(ctx)) return fail(RCDC_ERR_INVALID_INPUT, "ctx is NULL");
-    if (flags & ~RCDC_PLACE_SKIP_ZERO)
-        return fail(RCDC_ERR_INVALID_INPUT, "flags: unknown bits 0x%x", flags & ~RCDC_PLACE_SKIP_ZERO);
-    if (nblobs && !blobs) return fail(RCDC_ERR_INVALID_INPUT, "blobs is NULL with nblobs %u", nblobs);
-    if (ndests_total && !dests)
-        return fail(RCDC_ERR_INVALID_INPUT, "dests is NULL with ndests_total %u", ndests_total);
-    if (n_ins && (!d_ins || !in_lens))
-        return fail(RCDC_ERR_INVALID_INPUT, "%s is NULL with n_ins %u", d_ins ? "in_lens" : "d_ins",
-                    n_ins);
-    if (n_outs && (!d_outs || !out_lens))
-        return fail(RCDC_ERR_INVALID_INPUT, "%s is NULL with n_outs %u",
-                    d_outs ? "out_lens" : "d_outs", n_outs);
-    if (!nblobs) return RCDC_OK;
-
-    std::lock_guard<std::mutex> lk(ctx->place_mu);
-    DeviceGuard g(ctx->device);
-    // page-locked: every destination's device address, the non-zero words
-    // read back, the tiles
-    uint64_t ntiles = 0;
-    for (uint32_t i = 0; i < nblobs; i++) ntiles += (blobs[i].len >> 16) + 1;  // an upper bound
-    const uint64_t R = std::min<uint64_t>(ntiles, place_tile_cap());
-    const uint64_t o_nz = ((uint64_t)ndests_total * 8 + 15) / 16 * 16;
-    const uint64_t o_tiles = (o_nz + (uint64_t)nblobs * 4 + 31) / 32 * 32;
-    const uint64_t need = o_tiles + R * sizeof(PlaceTile);
-    if (need > ctx->cap_h_place) {
-        if (ctx->h_place) HIP_TRY(hipHostFree(ctx->h_place));
-        ctx->h_place = nullptr;
-        ctx->cap_h_place = 0;
-        const uint64_t c = need + need / 4 + 4096;
-        HIP_TRY(hipHostMalloc((void **)&ctx->h_place, c, hipHostMallocDefault));
-        ctx->cap_h_place = c;
-    }
-    uint64_t *daddr = reinterpret_cast<uint64_t *>(ctx->h_place);
-    uint32_t *h_nz = reinterpret_cast<uint32_t *>(ctx->h_place + o_nz);
-    PlaceTile *tiles = reinterpret_cast<PlaceTile *>(ctx->h_place + o_tiles);
-    for (uint32_t i = 0; i < nblobs; i++) {
-        const rcdc_place_blob &b = blobs[i];
-        if (b.src >= n_ins)
-            return fail(RCDC_ERR_INVALID_INPUT, "blob %u: src %u >= n_ins %u", i, b.src, n_ins);
-        if (b.len > in_lens[b.src] || b.in_off > in_lens[b.src] - b.len)
-            return fail(RCDC_ERR_INVALID_INPUT,
-                        "blob %u: in_off %llu + len %llu > in_lens[%u] = %llu", i,
-                        (unsigned long long)b.in_off, (unsigned long long)b.len, b.src,
-                        (unsigned long long)in_lens[b.src]);
-        if (b.len && !d_ins[b.src])
-            return fail(RCDC_ERR_INVALID_INPUT, "blob %u: d_ins[%u] is NULL", i, b.src);
-        if ((uint64_t)b.dest0 + b.ndests > ndests_total)
-            return fail(RCDC_ERR_INVALID_INPUT, "blob %u: dest0 %u + ndests %u > ndests_total %u", i,
-                        b.dest0, b.ndests, ndests_total);
-        for (uint32_t d = b.dest0; d < b.dest0 + b.ndests; d++) {
-            const rcdc_place_dest &o = dests[d];
-            if (o.dst >= n_outs)
-                return fail(RCDC_ERR_INVALID_INPUT, "blob %u, dest %u: dst %u >= n_outs %u", i, d,
-                            o.dst, n_outs);
-            if (b.len > out_lens[o.dst] || o.out_off > out_lens[o.dst] - b.len)
-                return fail(RCDC_ERR_INVALID_INPUT,
-                            "blob %u, dest %u: out_off %llu + len %llu > out_lens[%u] = %llu", i, d,
-                            (unsigned long long)o.out_off, (unsigned long long)b.len, o.dst,
-                            (unsigned long long)out_lens[o.dst]);
-            if (b.len && !d_outs[o.dst])
-                return fail(RCDC_ERR_INVALID_INPUT, "blob %u, dest %u: d_outs[%u] is NULL", i, d,
-                            o.dst);
-            daddr[d] = (uint64_t)(uintptr_t)d_outs[o.dst] + o.out_off;
-        }
-    }
-
-    const bool skip = (flags & RCDC_PLACE_SKIP_ZERO) != 0, want_zero = skip || zero;
-    hipStream_t st;
-    rcdc_status rs;
-    if ((rs = null_enter(ctx, hip_stream, &st))) return rs;
-    if ((rs = ctx->d_place_tiles.ensure(R))) return rs;
-    if ((rs = ctx->d_place_dests.ensure(std::max<uint64_t>(ndests_total, 1))))
-        return rs;
-    if (ndests_total)
-        HIP_TRY(hipMemcpyAsync(ctx->d_place_dests, daddr, (size_t)ndests_total * 8,
-                               hipMemcpyHostToDevice, st));
-    if (want_zero) {
-        if ((rs = ctx->d_place_nz.ensure(nblobs))) return rs;
-        HIP_TRY(hipMemsetAsync(ctx->d_place_nz, 0, (size_t)nblobs * 4, st));
-    }
-    if (!ctx->place_up) HIP_TRY(hipStreamCreateWithFlags(&ctx->place_up, hipStreamNonBlocking));
-    const uint32_t cus = (uint32_t)std::max(ctx->num_cus, 1);
-    bool whole = false;  // the device holds the tile list of the whole call,
-    uint64_t whole_n = 0;  // this many tiles
-    // one pass over all tiles: tiles [w0, pos) of the buffers are the window
-    // being built
-    auto pass = [&](bool write, bool zero_test, bool skip_zero) -> rcdc_status {
-        uint64_t pos = 0, w0 = 0, w = 4096, rounds = 0;
-        uint32_t win = 0;  // windows of this round
-        auto flush = [&]() -> rcdc_status {
-            if (pos == w0) return RCDC_OK;
-            // no window of a round overwrites another, and the round before
-            // has run: the upload need not wait for the kernels in flight
-            const bool side = win < sizeof ctx->place_ev / sizeof ctx->place_ev[0];
-            HIP_TRY(hipMemcpyAsync(ctx->d_place_tiles + w0, tiles + w0,
-                                   (pos - w0) * sizeof(PlaceTile), hipMemcpyHostToDevice,
-                                   side ? ctx->place_up : st));
-            if (side) {
-                hipEvent_t &ev = ctx->place_ev[win];
-                if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                HIP_TRY(hipEventRecord(ev, ctx->place_up));
-                HIP_TRY(hipStreamWaitEvent(st, ev, 0));
-            }
-            win++;
-            HIP_TRY(launch_place(ctx->d_place_tiles + w0, (uint32_t)(pos - w0), ctx->d_place_dests,
-                                 ctx->d_place_nz, write, zero_test, skip_zero, cus, st));
-            w0 = pos;
-            w *= 2;
-            return RCDC_OK;
-        };
-        for (uint32_t i = 0; i < nblobs; i++) {
-            const rcdc_place_blob &b = blobs[i];
-            if (!b.len || (!zero_test && !b.ndests)) continue;
-            const uint64_t src = (uint64_t)(uintptr_t)d_ins[b.src] + b.in_off;
-            uint64_t aligned = kPlaceAligned;
-            for (uint32_t d = b.dest0; d < b.dest0 + b.ndests; d++)
-                if ((daddr[d] ^ src) & 15u) aligned = 0;
-            for (uint64_t c = 0; c < b.len; c += kPlaceTile) {
-                if (pos == R) {
-                    // the buffers are full: a new round once this one has run
-                    if (rcdc_status fs = flush()) return fs;
-                    HIP_TRY(poll_stream(st));
-                    pos = w0 = 0;
-                    win = 0;
-                    rounds++;
-                }
-                PlaceTile &t = tiles[pos++];
-                t.src = src + c;
-                t.len = (uint32_t)std::min<uint64_t>(kPlaceTile, b.len - c);
-                t.blob = i;
-                t.dest0 = b.dest0;
-                t.ndests = b.ndests;
-                t.off = c | aligned;
-                if (pos - w0 >= w)
-                    if (rcdc_status fs = flush()) return fs;
-            }
-        }
-        whole = rounds == 0 && zero_test;  // (a pass without the zero test leaves blobs out)
-        whole_n = pos;
-        return flush();
-    };
-    if (skip) {
-        // every tile of a blob has been tested before any of it is written
-        if ((rs = pass(false, true, false))) return rs;
-        if (whole) {
-            // the same list again: tiles of blobs without a destination fall out in the kernel
-            HIP_TRY(launch_place(ctx->d_place_tiles, (uint32_t)whole_n, ctx->d_place_dests,
-                                 ctx->d_place_nz, true, false, true, cus, st));
-        } else {
-            HIP_TRY(poll_stream(st));  // the first pass's uploads have left the host buffer
-            if ((rs = pass(true, false, true))) return rs;
-        }
-    } else {
-        if ((rs = pass(true, want_zero, false))) return rs;
-    }
-    if (zero)
-        HIP_TRY(hipMemcpyAsync(h_nz, ctx->d_place_nz, (size_t)nblobs * 4, hipMemcpyDeviceToHost,
-                               st));
-    HIP_TRY(poll_stream(st));
-    if (zero)
-        for (uint32_t i = 0; i < nblobs; i++) zero[i] = h_nz[i] ? 0 : 1;
-    return null_leave(ctx, hip_stream, st);
-}
-
-uint64_t rcdc_zstd_bound(uint64_t len) {
-    return len + 3 * zstd_blocks(len) + (len > kZstdSingleMax ? 10 : 9);  // + the window byte
-}
-
-rcdc_status rcdc_zstd_compress(rcdc_ctx *ctx, int level, const void *d_in,
-                               const rcdc_zstd_ref *refs, uint32_t n, void *d_out,
-                               uint64_t *out_lens, void *hip_stream) {
-    return zstd_compress(ctx, level, d_in, refs, n, d_out, out_lens, hip_stream);
-}
-
-void rcdc_zstd_tables(void *out) { memcpy(out, &zstd_tables(), sizeof(ZstdTables)); }
-
-uint64_t rcdc_zstd_tables_size(void) { return sizeof(ZstdTables); }
 
 // ---- streaming: one file fed in pieces -------------------------------------
 
