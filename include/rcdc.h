@@ -936,6 +936,116 @@ rcdc_status rcdc_index_parse(rcdc_ctx *ctx, const void *d_json, uint64_t json_le
                              rcdc_ixparse_file *files, rcdc_ixparse_pack *packs,
                              uint64_t cap_packs, rcdc_ixparse_result *result, void *hip_stream);
 
+/* ---- index files written on the device (repofile/indexfile.rs) ------------
+ * The reverse of rcdc_index_parse: for a batch of index files whose blobs are
+ * entries in HBM, the bytes serde_json::to_vec(&IndexFile) writes, into one
+ * device arena.  No byte of the text and no entry reaches the host; only the
+ * per-file (off, len) and the total come back.
+ *
+ * Text, byte for byte (no whitespace anywhere, integers in plain decimal,
+ * ids as 64 lower-case hex digits):
+ *   root  {  then "supersedes":[id,...],  only when the file has a supersedes
+ *         list (an empty one writes []), then "packs":[pack,...], then
+ *         ,"packs_to_delete":[pack,...] only when that list is not empty, }
+ *   pack  {"id":id,"blobs":[blob,...]  then ,"time":"<text>" when it has a
+ *         time, then ,"size":<int> when it has a size, }
+ *   blob  {"id":id,"type":"data"|"tree","offset":<int>,"length":<int>,
+ *         "uncompressed_length":<int>|null}
+ *         the last key is always there; an uncompressed length of 0 writes
+ *         null; every blob of a pack carries the pack's type.
+ *
+ * Entries (device), by strides in bytes exactly as rcdc_prune_set_entries
+ * takes them: entry e has its id at d_ids + e * id_stride and its uint32
+ * offset, length and uncompressed length at d_offset + e * offset_stride,
+ * d_len + e * len_stride, d_ulen + e * ulen_stride.  The integer arrays and
+ * their strides must be 4-byte aligned; so the d_ids[t] / d_locs[t] of
+ * rcdc_index_parse pass as they are.  n_entries is the arrays' length.
+ *
+ * packs, files, supersedes (n_supersedes x 32 bytes) and times (time_bytes
+ * of text) are host memory; the call uploads them.  A pack record names its
+ * entries [first, first + count); ranges may lie anywhere in the arrays and
+ * one range may be written by several records.  A file record names its
+ * pack records [pack_first, pack_first + pack_count), of which the last
+ * n_delete are its packs_to_delete, and its supersedes ids [sup_first,
+ * sup_first + sup_count) when has_supersedes is set.  A time is the bytes
+ * times[time_off .. time_off + time_len): at most RCDC_IXWRITE_MAX_TIME of
+ * them, each in 0x20..0x7E and neither '"' nor '\' (the string of
+ * rcdc_index_parse's grammar, so what is written parses back there).
+ *
+ * Output: file i lies at d_out + out[i].off, out[i].len bytes, the offsets
+ * 16-byte aligned and in file order (out[0].off == 0, out[i + 1].off ==
+ * out[i].off + out[i].len rounded up to 16); *total is the end of the last
+ * file.  out and total are host memory.  Every byte of a file is written
+ * exactly once; no other byte of d_out is written, neither the gap up to the
+ * next 16-byte boundary nor anything behind the last file.
+ *
+ * Bound (rcdc_index_write_bound): the largest blob object,
+ *   {"id":"<64>","type":"data","offset":4294967295,"length":4294967295,
+ *    "uncompressed_length":4294967295}
+ * has 130 + 3 * 10 = 160 bytes, 161 with its comma.  The largest pack object
+ * without its blobs and its time text is {"id":"<64>","blobs":[] (82 + 1),
+ * ,"time":"" (10), ,"size":4294967295 (18), } (1) and a comma: 113 bytes.
+ * A supersedes id is 66 bytes and a comma.  The root's own text is at most
+ * {"supersedes":[], (17) "packs":[ (9) ],"packs_to_delete":[ (21) ]} (2):
+ * 49 bytes, and the padding to the next file is at most 15.  So
+ *   161 n_entries + 113 n_packs + time_bytes + 67 n_supersedes + 64 n_files
+ * always suffices, the counts being those WRITTEN: the sum of count over
+ * the pack records of all files, the sum of pack_count, of the time_len of
+ * those packs, and of sup_count.  cap_out must be at least that.
+ *
+ * Stages, the parser's in reverse: a size pass, one lane per written entry;
+ * device scans of the entry sizes, then of the pack sizes, then of the file
+ * lengths into aligned offsets; an emit pass in which one wave owns a span
+ * of RCDC_IXWRITE_SPAN bytes of d_out (counted from d_out, which must be
+ * 16-byte aligned), its lanes format the objects that touch the span into
+ * LDS at their places, and the span leaves with 16-byte stores; only a
+ * file's last, ragged 16 bytes go byte by byte.
+ *
+ * The work is queued on hip_stream and the call returns once it has drained.
+ * RCDC_ERR_INVALID_INPUT before anything is launched or written: a null
+ * context, a null array with a non-zero count, out or total null, a range
+ * past its array, unaligned integer arrays or strides, an unaligned d_out,
+ * a type above 1, a flag other than the two below, a time outside the
+ * string above, n_delete above pack_count, 2^32 - 1 written entries or pack
+ * records or more, cap_out below the bound.  n_files == 0 launches nothing
+ * and gives *total = 0.                                                      */
+#define RCDC_IXWRITE_SPAN     8192u
+#define RCDC_IXWRITE_MAX_TIME 64u
+#define RCDC_IXWRITE_HAS_TIME 1u
+#define RCDC_IXWRITE_HAS_SIZE 2u
+typedef struct {
+    uint8_t id[32];
+    uint64_t first;      /* its entries are [first, first + count)        */
+    uint32_t count;
+    uint32_t type;       /* 0 data, 1 tree: the type every blob is given  */
+    uint32_t flags;      /* RCDC_IXWRITE_HAS_TIME | RCDC_IXWRITE_HAS_SIZE */
+    uint32_t size;
+    uint32_t time_off, time_len; /* into times                            */
+} rcdc_ixwrite_pack; /* 64 B */
+typedef struct {
+    uint64_t pack_first;
+    uint32_t pack_count; /* pack records, packs_to_delete included        */
+    uint32_t n_delete;   /* the last n_delete of them are packs_to_delete */
+    uint64_t sup_first;
+    uint32_t sup_count;
+    uint32_t has_supersedes;
+} rcdc_ixwrite_file; /* 32 B */
+typedef struct {
+    uint64_t off, len;
+} rcdc_ixwrite_out; /* 16 B */
+
+uint64_t rcdc_index_write_bound(uint64_t n_entries, uint64_t n_packs, uint64_t n_files,
+                                uint64_t n_supersedes, uint64_t time_bytes);
+uint32_t rcdc_index_write_span(void); /* == RCDC_IXWRITE_SPAN */
+rcdc_status rcdc_index_write(rcdc_ctx *ctx, const void *d_ids, uint64_t id_stride,
+                             const void *d_offset, uint64_t offset_stride, const void *d_len,
+                             uint64_t len_stride, const void *d_ulen, uint64_t ulen_stride,
+                             uint64_t n_entries, const rcdc_ixwrite_pack *packs, uint64_t n_packs,
+                             const rcdc_ixwrite_file *files, uint32_t n_files,
+                             const uint8_t *supersedes, uint64_t n_supersedes, const char *times,
+                             uint64_t time_bytes, void *d_out, uint64_t cap_out,
+                             rcdc_ixwrite_out *out, uint64_t *total, void *hip_stream);
+
 /* ---- prune's plan on the device (commands/prune.rs) -------------------------
  * The per-blob part of PrunePlan::from_prune_options for index entries that
  * are in HBM: count_used_blobs (prune.rs:770-784), the sequential marking of

@@ -20,6 +20,9 @@ from .repack import (  # noqa: F401
 from .prune import (  # noqa: F401
     LimitOption, PackStatus, PackToDo, PrunePlan, PruneOptions, PruneStats,
 )
+from .index_write import (  # noqa: F401
+    DeviceIndexer, FileRecord, PackRecord, WrittenJson, save_index_files, write_json,
+)
 
 __all__ = [
     "ErrorKind", "RusticError", "Chunker", "ChunkIter", "ConfigFile", "Context",
@@ -27,4 +30,5 @@ __all__ = [
     "RestorePlan", "index_lookup", "restore_contents", "DeviceIndex", "IndexType",
     "BlobCopier", "CopyPackBlobs", "CopyStats", "NewPack", "plan_copy", "plan_repack",
     "LimitOption", "PackStatus", "PackToDo", "PrunePlan", "PruneOptions", "PruneStats",
+    "DeviceIndexer", "FileRecord", "PackRecord", "WrittenJson", "save_index_files", "write_json",
 ]

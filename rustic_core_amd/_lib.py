@@ -46,6 +46,7 @@ EXPORTS = (
     "rcdc_index_parse", "rcdc_index_parse_bound", "rcdc_index_parse_tile",
     "rcdc_prune_create", "rcdc_prune_destroy", "rcdc_prune_set_entries", "rcdc_prune_mark",
     "rcdc_prune_keep",
+    "rcdc_index_write", "rcdc_index_write_bound", "rcdc_index_write_span",
 )
 ABI_VERSION = 5
 
@@ -103,6 +104,26 @@ class IxparseResult(ctypes.Structure):
     """rcdc_ixparse_result."""
     _fields_ = [("packs", ctypes.c_uint64 * 2), ("entries", ctypes.c_uint64 * 2),
                 ("files_not_parsed", ctypes.c_uint64)]
+
+
+class IxwritePack(ctypes.Structure):
+    """rcdc_ixwrite_pack."""
+    _fields_ = [("id", ctypes.c_uint8 * 32), ("first", ctypes.c_uint64),
+                ("count", ctypes.c_uint32), ("type", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("size", ctypes.c_uint32),
+                ("time_off", ctypes.c_uint32), ("time_len", ctypes.c_uint32)]
+
+
+class IxwriteFile(ctypes.Structure):
+    """rcdc_ixwrite_file."""
+    _fields_ = [("pack_first", ctypes.c_uint64), ("pack_count", ctypes.c_uint32),
+                ("n_delete", ctypes.c_uint32), ("sup_first", ctypes.c_uint64),
+                ("sup_count", ctypes.c_uint32), ("has_supersedes", ctypes.c_uint32)]
+
+
+class IxwriteOut(ctypes.Structure):
+    """rcdc_ixwrite_out."""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
 
 class PruneResult(ctypes.Structure):
@@ -326,6 +347,13 @@ def lib() -> ctypes.CDLL:
     L.rcdc_prune_mark.argtypes = [vp, vp, vp, vp, P(PruneResult), vp]
     L.rcdc_prune_keep.restype = st
     L.rcdc_prune_keep.argtypes = [vp, vp, vp, vp, vp]
+    L.rcdc_index_write_bound.restype = u64
+    L.rcdc_index_write_bound.argtypes = [u64, u64, u64, u64, u64]
+    L.rcdc_index_write_span.restype = u32
+    L.rcdc_index_write_span.argtypes = []
+    L.rcdc_index_write.restype = st
+    L.rcdc_index_write.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, vp, u64, vp, u32,
+                                   vp, u64, vp, u64, vp, u64, vp, P(u64), vp]
     _lib = L
     return L
 

@@ -18,8 +18,13 @@ Reference:
   prefixes ``2`` + a zstd frame in version-2 repositories before sealing;
   the file id is the SHA-256 of the sealed bytes (``hash_write_full``).
 
-The JSON is host work (kilobytes per pack); the compression and sealing of
-the file go through the device (``compress.encode_all``, ``crypto.Key``).
+Here the JSON is host work, one file at a time (``IndexFile.to_json``); the
+compression and sealing of the file go through the device
+(``compress.encode_all``, ``crypto.Key``).  For packs whose blobs are entries
+in HBM the text is written on the device too: ``index_write.write_json``,
+``save_index_files`` and ``DeviceIndexer`` are this module's ``to_json``,
+``save_index_file`` and ``Indexer`` for a whole batch, and are tested against
+them.
 """
 from __future__ import annotations
 

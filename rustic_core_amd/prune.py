@@ -14,7 +14,10 @@ the device over entry arrays in HBM (``DevicePrune``); ``device=None`` runs
 the same rule in plain Python in the reference's sequential shape, which is
 what the device is tested against.  The per-pack part (thresholds, the
 candidate sort, one running sum) is host work either way.  Finding the used
-ids, writing index files and deleting packs stay with the caller.
+ids and deleting packs stay with the caller; ``index_updates`` is the loop
+of ``do_prune`` that rebuilds the index (:1230-1353) as data, and
+``write_index`` feeds it to an ``index_write.DeviceIndexer`` over the plan's
+own entry arrays, so the new index files are written on the device.
 """
 from __future__ import annotations
 
@@ -223,6 +226,14 @@ class PruneIndex:
 
     def __len__(self) -> int:
         return sum(p.count for p in self.packs)
+
+
+@dataclass
+class IndexUpdates:
+    """What ``PrunePlan.index_updates`` gives."""
+    adds: list            # (index_write.PackRecord, delete flag) in add order
+    delete_packs: dict    # blob type -> pack ids to remove from the backend
+    delete_unindexed: list  # existing_packs removed at once (instant_delete)
 
 
 def _ns(t) -> Optional[int]:
@@ -470,6 +481,7 @@ class PrunePlan:
         self.packs: List[PrunePack] = []
         self.stats = PruneStats()
         self.index_files: List[PruneIndex] = []
+        self.existing_packs: Dict[bytes, int] = {}
         self.rounds = 0
 
     # ---- constructors ---------------------------------------------------------
@@ -795,6 +807,8 @@ class PrunePlan:
                                       f"expected size `{p.size}` in the index file. ")
         self.stats.size_unref = sum(existing.values())
         self.stats.packs_unref = len(existing)
+        # what is left are packs no index file knows (a BTreeMap: in id order)
+        self.existing_packs = dict(sorted(existing.items()))
 
     # ---- filter_index_files (prune.rs:1122-1149) -----------------------------------------
     def _filter_index_files(self, instant_delete: bool) -> None:
@@ -835,6 +849,79 @@ class PrunePlan:
             blobs.sort(key=_blob_order)
             out.append((p, _coalesced(CopyPackBlobs.from_index_entry(p.id, b) for b in blobs)))
         return out
+
+    def index_updates(self, prune_time: str, instant_delete: bool = False) -> "IndexUpdates":
+        """The index half of ``do_prune`` (prune.rs:1230-1353) as data.
+        ``adds``: (PackRecord, delete flag) in the order the reference gives
+        packs to its indexer -- first a removal record per pack of
+        ``existing_packs`` (``size`` set, no blobs, ``time = prune_time``)
+        unless ``instant_delete``, then every pack of ``index_files``
+        according to its ``to_do``: ``into_index_pack`` keeps a pack's time
+        and sets ``prune_time`` where it has none, ``into_index_pack_with_time``
+        sets ``prune_time``; ``size`` is absent.  ``delete_packs``: per blob
+        type, the packs to remove from the backend (``Delete`` packs, and
+        with ``instant_delete`` every pack that would else be marked);
+        ``delete_unindexed``: the ``existing_packs`` that ``instant_delete``
+        removes.  Nothing is to do when ``index_files`` is empty (:1260-1263):
+        only the removal records are given then."""
+        from .index_write import PackRecord
+        up = IndexUpdates([], {DATA: [], TREE: []}, [])
+        if self.existing_packs:
+            if instant_delete:
+                up.delete_unindexed = list(self.existing_packs)
+            else:
+                for pid, size in self.existing_packs.items():
+                    up.adds.append((PackRecord(pid, DATA, 0, 0, prune_time, size), True))
+        T = PackToDo
+        for index in self.index_files:
+            for p in index.packs:
+                keep_time = PackRecord(p.id, p.blob_type, p.first, p.count,
+                                       p.time if p.time is not None else prune_time, None)
+                new_time = keep_time._replace(time=prune_time)
+                if p.to_do == T.Undecided:
+                    raise RusticError(ErrorKind.Internal,
+                                      f"Pack `{p.id.hex()}` got no decision what to do with it!")
+                if p.to_do == T.Keep:
+                    up.adds.append((keep_time, False))
+                elif p.to_do in (T.Repack, T.MarkDelete):
+                    if instant_delete:
+                        up.delete_packs[p.blob_type].append(p.id)
+                    else:
+                        up.adds.append((new_time, True))
+                elif p.to_do in (T.KeepMarked, T.KeepMarkedAndCorrect):
+                    if instant_delete:
+                        up.delete_packs[p.blob_type].append(p.id)
+                    else:
+                        up.adds.append((keep_time, True))
+                elif p.to_do == T.Recover:
+                    up.adds.append((new_time, False))
+                else:  # Delete
+                    up.delete_packs[p.blob_type].append(p.id)
+        return up
+
+    def write_index(self, key, indexer=None, prune_time: Optional[str] = None,
+                    instant_delete: Optional[bool] = None, save=None, device: Optional[int] = None,
+                    **indexer_args):
+        """``index_updates`` fed into a ``DeviceIndexer`` over the plan's own
+        entry arrays (``indexer``, or a new one made with ``save``, ``key``
+        and ``indexer_args``).  Returns the indexer, not finalized, with the
+        IndexUpdates as its ``updates``: the caller runs
+        ``BlobCopier(.., indexer=it)`` over ``repack_plans()`` and finalizes
+        it, as prune.rs:1356-1431 does."""
+        from .index import rustic_time
+        from .index_write import DeviceIndexer
+        if instant_delete is None:
+            instant_delete = self._opts.instant_delete
+        if device is None:
+            device = self._dev.index if getattr(self, "_dev", None) is not None else 0
+        if indexer is None:
+            indexer = DeviceIndexer(save, device=int(device or 0), key=key, **indexer_args)
+        up = self.index_updates(prune_time or rustic_time(), instant_delete)
+        entries = (self._ids, self._offsets, self._lens, self._ulens)
+        for rec, delete in up.adds:
+            indexer.add(rec, delete, entries=entries)
+        indexer.updates = up
+        return indexer
 
     def size_after_prune(self) -> Dict[int, int]:
         """prune.rs:1373-1377."""
