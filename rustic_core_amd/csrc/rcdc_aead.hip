@@ -12,7 +12,8 @@
 // independent AES chains; the next step's data already loading): counter
 // block = nonce + block index (128-bit big-endian), AES-256 by T-tables in
 // LDS, keystream XOR data, and the ciphertext block goes into the lane's
-// Poly1305 accumulator by Horner with R = r^64 (26-bit limbs).  The lanes
+// Poly1305 accumulator by Horner with R = r^64 (26-bit limbs: rcdc_p1305.h, which states every limb
+// bound the steps below rely on).  The lanes
 // combine with r^(unit end - lane's last block) and a wave reduction; the
 // unit's partial is positioned with r^(blocks after the unit) (binary powers
 // of r).  rcdc_aead_finish_kernel sums a blob's partials mod 2^130 - 5, adds
@@ -32,8 +33,10 @@
 
 #include "rcdc_internal.h"
 #include "rcdc_launch.h"
+#include "rcdc_p1305.h"
 
 using namespace rcdc;
+using namespace rcdc::p1305;
 
 namespace rcdc {
 // 16 waves, one workgroup per CU (the 128 KiB of tables): 4 waves per SIMD,
@@ -47,72 +50,6 @@ namespace {
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_amdgcn_perm(x, x, 0x00010203u); }
 __device__ __forceinline__ uint32_t ror32(uint32_t x, int k) { return __builtin_amdgcn_alignbit(x, x, k); }
-
-struct P26 {
-    uint32_t h[5];
-};
-
-// a * b mod 2^130 - 5 (limbs of a below ~2^27, of b below 2^26; result limbs
-// below 2^26 + a few).
-__device__ __forceinline__ P26 pmul(const P26 &a, const uint32_t *b) {
-    const uint64_t b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3], b4 = b[4];
-    const uint64_t s1 = b1 * 5, s2 = b2 * 5, s3 = b3 * 5, s4 = b4 * 5;
-    const uint64_t a0 = a.h[0], a1 = a.h[1], a2 = a.h[2], a3 = a.h[3], a4 = a.h[4];
-    uint64_t d0 = a0 * b0 + a1 * s4 + a2 * s3 + a3 * s2 + a4 * s1;
-    uint64_t d1 = a0 * b1 + a1 * b0 + a2 * s4 + a3 * s3 + a4 * s2;
-    uint64_t d2 = a0 * b2 + a1 * b1 + a2 * b0 + a3 * s4 + a4 * s3;
-    uint64_t d3 = a0 * b3 + a1 * b2 + a2 * b1 + a3 * b0 + a4 * s4;
-    uint64_t d4 = a0 * b4 + a1 * b3 + a2 * b2 + a3 * b1 + a4 * b0;
-    P26 r;
-    d1 += d0 >> 26;
-    r.h[0] = (uint32_t)d0 & 0x3ffffff;
-    d2 += d1 >> 26;
-    r.h[1] = (uint32_t)d1 & 0x3ffffff;
-    d3 += d2 >> 26;
-    r.h[2] = (uint32_t)d2 & 0x3ffffff;
-    d4 += d3 >> 26;
-    r.h[3] = (uint32_t)d3 & 0x3ffffff;
-    const uint64_t c = d4 >> 26;
-    r.h[4] = (uint32_t)d4 & 0x3ffffff;
-    const uint64_t t0 = (uint64_t)r.h[0] + c * 5;
-    r.h[0] = (uint32_t)t0 & 0x3ffffff;
-    r.h[1] += (uint32_t)(t0 >> 26);
-    return r;
-}
-
-__device__ __forceinline__ void pnorm(P26 &a) {
-    uint32_t c;
-    c = a.h[0] >> 26; a.h[0] &= 0x3ffffff; a.h[1] += c;
-    c = a.h[1] >> 26; a.h[1] &= 0x3ffffff; a.h[2] += c;
-    c = a.h[2] >> 26; a.h[2] &= 0x3ffffff; a.h[3] += c;
-    c = a.h[3] >> 26; a.h[3] &= 0x3ffffff; a.h[4] += c;
-    c = a.h[4] >> 26; a.h[4] &= 0x3ffffff; a.h[0] += c * 5;
-    c = a.h[0] >> 26; a.h[0] &= 0x3ffffff; a.h[1] += c;
-}
-
-// The 16-byte message block w (4 little-endian words) plus 2^(8 k), k the
-// block's byte count (16: the 2^128 bit).
-__device__ __forceinline__ P26 pblock(const uint32_t w[4], uint32_t k) {
-    uint32_t x[4] = {w[0], w[1], w[2], w[3]};
-    uint32_t hib = 0;
-    if (k < 16) {  // partial final block: bytes >= k are zero, then the 1 byte
-        for (int i = 0; i < 4; i++) {
-            const int lo = 4 * i;
-            if ((int)k <= lo) x[i] = 0;
-            else if ((int)k < lo + 4) x[i] &= (1u << (8 * (k - lo))) - 1u;
-        }
-        x[k >> 2] |= 1u << (8 * (k & 3));
-    } else {
-        hib = 1;
-    }
-    P26 m;
-    m.h[0] = x[0] & 0x3ffffff;
-    m.h[1] = ((x[0] >> 26) | (x[1] << 6)) & 0x3ffffff;
-    m.h[2] = ((x[1] >> 20) | (x[2] << 12)) & 0x3ffffff;
-    m.h[3] = ((x[2] >> 14) | (x[3] << 18)) & 0x3ffffff;
-    m.h[4] = (x[3] >> 8) | (hib << 24);
-    return m;
-}
 
 // a ^ b ^ c in one VALU op (gfx950 v_bitop3_b32, truth table 0x96)
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
@@ -247,24 +184,6 @@ __device__ __forceinline__ void blob_nonce(const uint8_t *in, const AeadBlob &B,
         load16(in + B.in_off, n);
     } else {
         n[0] = B.nonce[0]; n[1] = B.nonce[1]; n[2] = B.nonce[2]; n[3] = B.nonce[3];
-    }
-}
-
-// Carry-propagate and wrap until every limb is below 2^26 and the value is
-// below 2^130 (limbs on entry below 2^31).
-__device__ __forceinline__ void pfull(P26 &a) {
-    for (int rep = 0; rep < 2; rep++) {
-        for (int j = 0; j < 4; j++) {
-            a.h[j + 1] += a.h[j] >> 26;
-            a.h[j] &= 0x3ffffff;
-        }
-        const uint32_t c = a.h[4] >> 26;
-        a.h[4] &= 0x3ffffff;
-        a.h[0] += c * 5;
-    }
-    for (int j = 0; j < 4; j++) {
-        a.h[j + 1] += a.h[j] >> 26;
-        a.h[j] &= 0x3ffffff;
     }
 }
 
@@ -408,19 +327,6 @@ __global__ __launch_bounds__(256) void rcdc_aead_finish_kernel(
         pnorm(h);
     }
     pfull(h);
-    // h mod p: h - p if h >= p
-    uint32_t g[5];
-    uint32_t c = 5;
-    for (int j = 0; j < 5; j++) {
-        const uint32_t t = h.h[j] + c;
-        g[j] = t & 0x3ffffff;
-        c = t >> 26;
-    }
-    if (c) {  // h + 5 >= 2^130
-        for (int j = 0; j < 5; j++) h.h[j] = g[j];
-    }
-    const uint64_t lo = (uint64_t)h.h[0] | (uint64_t)h.h[1] << 26 | (uint64_t)h.h[2] << 52;
-    const uint64_t hi = (uint64_t)(h.h[2] >> 12) | (uint64_t)h.h[3] << 14 | (uint64_t)h.h[4] << 40;
     // s = AES-128_k(nonce): byte-oriented T-table lookups (one block per blob)
     uint32_t nonce[4];
     blob_nonce<OPEN>(in, B, nonce);
@@ -454,13 +360,8 @@ __global__ __launch_bounds__(256) void rcdc_aead_finish_kernel(
     // s as a little-endian 128-bit number (its bytes in order)
     const uint64_t slo = (uint64_t)bswap32(f1) << 32 | bswap32(f0);
     const uint64_t shi = (uint64_t)bswap32(f3) << 32 | bswap32(f2);
-    const uint64_t tlo = lo + slo;
-    const uint64_t thi = hi + shi + (tlo < lo ? 1 : 0);
     uint8_t tag[16];
-    for (int j = 0; j < 8; j++) {
-        tag[j] = (uint8_t)(tlo >> (8 * j));
-        tag[8 + j] = (uint8_t)(thi >> (8 * j));
-    }
+    ptag(h, slo, shi, tag);
     if (OPEN) {
         const uint8_t *t = in + B.in_off + 16 + B.len;
         uint32_t d = 0;

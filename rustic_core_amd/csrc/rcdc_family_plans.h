@@ -16,6 +16,7 @@
 #include "../../include/rcdc.h"
 #include "rcdc_place.h"
 #include "rcdc_internal.h"
+#include "rcdc_p1305.h"
 
 namespace rcdc {
 namespace plans {
@@ -72,29 +73,6 @@ inline void aes_expand_host(const uint8_t *key, int nk, const uint8_t sb[256], u
     }
 }
 
-// 2^130 - 5 arithmetic in 26-bit limbs (the device pmul, on the host)
-inline void p26_mul(const uint32_t a[5], const uint32_t b[5], uint32_t r[5]) {
-    const uint64_t b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3], b4 = b[4];
-    const uint64_t s1 = b1 * 5, s2 = b2 * 5, s3 = b3 * 5, s4 = b4 * 5;
-    const uint64_t a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4];
-    uint64_t d0 = a0 * b0 + a1 * s4 + a2 * s3 + a3 * s2 + a4 * s1;
-    uint64_t d1 = a0 * b1 + a1 * b0 + a2 * s4 + a3 * s3 + a4 * s2;
-    uint64_t d2 = a0 * b2 + a1 * b1 + a2 * b0 + a3 * s4 + a4 * s3;
-    uint64_t d3 = a0 * b3 + a1 * b2 + a2 * b1 + a3 * b0 + a4 * s4;
-    uint64_t d4 = a0 * b4 + a1 * b3 + a2 * b2 + a3 * b1 + a4 * b0;
-    d1 += d0 >> 26; d2 += d1 >> 26; d3 += d2 >> 26; d4 += d3 >> 26;
-    uint64_t h0 = (d0 & 0x3ffffff) + (d4 >> 26) * 5;
-    r[1] = (uint32_t)((d1 & 0x3ffffff) + (h0 >> 26));
-    r[0] = (uint32_t)(h0 & 0x3ffffff);
-    r[2] = (uint32_t)(d2 & 0x3ffffff);
-    r[3] = (uint32_t)(d3 & 0x3ffffff);
-    r[4] = (uint32_t)(d4 & 0x3ffffff);
-    // fully normalise (r[1] may carry)
-    const uint32_t c = r[1] >> 26;
-    r[1] &= 0x3ffffff;
-    r[2] += c;
-}
-
 inline void aead_key_material(const uint8_t key[64], AeadKeyDev *K) {
     uint8_t sb[256];
     aes_sbox(sb);
@@ -117,11 +95,20 @@ inline void aead_key_material(const uint8_t key[64], AeadKeyDev *K) {
     const uint32_t r[5] = {(uint32_t)(t0 & 0x3ffffff), (uint32_t)((t0 >> 26) & 0x3ffffff),
                            (uint32_t)(((t0 >> 52) | (t1 << 12)) & 0x3ffffff),
                            (uint32_t)((t1 >> 14) & 0x3ffffff), (uint32_t)((t1 >> 40) & 0x3ffffff)};
+    // table rows: the shared pmul, then pfull, so every limb is below 2^26 (the
+    // bound of pmul's b operand, rcdc_p1305.h)
+    auto mul = [](const uint32_t a[5], const uint32_t b[5], uint32_t out[5]) {
+        p1305::P26 x;
+        memcpy(x.h, a, sizeof x.h);
+        x = p1305::pmul(x, b);
+        p1305::pfull(x);
+        memcpy(out, x.h, sizeof x.h);
+    };
     const uint32_t one[5] = {1, 0, 0, 0, 0};
     memcpy(K->rpow[0], one, sizeof one);
-    for (int i = 1; i <= 64; i++) p26_mul(K->rpow[i - 1], r, K->rpow[i]);
+    for (int i = 1; i <= 64; i++) mul(K->rpow[i - 1], r, K->rpow[i]);
     memcpy(K->r2j[0], r, sizeof r);
-    for (int j = 1; j < 32; j++) p26_mul(K->r2j[j - 1], K->r2j[j - 1], K->r2j[j]);
+    for (int j = 1; j < 32; j++) mul(K->r2j[j - 1], K->r2j[j - 1], K->r2j[j]);
 }
 
 // ---- blob encryption: batches, pack files --------------------------------------

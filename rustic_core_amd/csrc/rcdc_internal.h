@@ -241,8 +241,8 @@ constexpr uint32_t kAeadUnitBlocks = 4096;  // 16-byte blocks per wave work unit
 struct AeadKeyDev {
     uint32_t rk256[60];    // AES-256 round keys (big-endian column words)
     uint32_t rk128[44];    // AES-128 round keys of Poly1305-AES's k
-    uint32_t rpow[65][5];  // r^0 .. r^64, 26-bit limbs (r clamped)
-    uint32_t r2j[32][5];   // r^(2^j)
+    uint32_t rpow[65][5];  // r^0 .. r^64, 26-bit limbs (r clamped), each below 2^26
+    uint32_t r2j[32][5];   // r^(2^j), limbs as rpow's (rcdc_p1305.h: pmul's b)
     uint32_t te[256];      // T-table: (2S, S, S, 3S) as a big-endian word
 };
 

@@ -48,6 +48,26 @@ def test_poly1305_rfc8439(oracle_mod):
         "a8061dc1305136c6c22b8baf0c0127a9"
 
 
+def test_poly1305_edges_against_integers(oracle_mod):
+    """The oracle's Poly1305 against Python integers on the crafted keys and
+    messages of tests/p1305_cases.py (sums at p and 2^130, r of 0, 1, a single
+    bit and the largest clamped value, unclamped key bytes, fills of 0xff, every
+    length the device kernel changes path at), with s at the carries of the
+    final 128-bit addition: the device edge tests rely on it for whole blobs."""
+    from tests.p1305_cases import M128, P, clamp, le128, mac_cases, mac_sums, poly_sum
+    cases, sums = mac_cases(), mac_sums()
+    assert len(cases) == 15 + 7 * 3 * 16
+    for name, r16, msg in cases:
+        for s in (0, (1 << 64) - 1, 1 << 64, M128):
+            want = le128((sums[name] + s) & M128)
+            assert oracle_mod.poly1305(r16, le128(s), msg) == want, (name, hex(s))
+    # the helper itself on the RFC 8439 2.5.2 vector
+    r = bytes.fromhex("85d6be7857556d337f4452fe42d506a8")
+    s = int.from_bytes(bytes.fromhex("0103808afb0db2fd4abff6af4149f51b"), "little")
+    h = poly_sum(clamp(r), b"Cryptographic Forum Research Group")
+    assert h < P and le128((h + s) & M128).hex() == "a8061dc1305136c6c22b8baf0c0127a9"
+
+
 @pytest.mark.parametrize("name", ["key1", "key2"])
 def test_reference_key_files_and_config(oracle_mod, name):
     """keys.rs:12-35: key1/key2 open with "test"/"test2", a wrong password

@@ -220,6 +220,13 @@ def _fixture_key(oracle_mod):
 def test_key_material(check, oracle_mod):
     keys = [bytes(64), bytes(range(64)), _fixture_key(oracle_mod)]
     assert len(keys[2]) == 64
+    # r at its edges: 0, 1, 2, the largest clamped value, sixteen 0xff bytes (the
+    # clamp makes them that value) and only the top nibble (the clamp clears it)
+    rmax = 0x0ffffffc0ffffffc0ffffffc0fffffff
+    edge = [0, 1, 2, rmax, (1 << 128) - 1, 1 << 124]
+    keys += [bytes(range(7, 55)) + v.to_bytes(16, "little") for v in edge]
+    clamped = [int.from_bytes(k[48:], "little") & rmax for k in keys[3:]]
+    assert clamped == [0, 1, 2, rmax, rmax, 0]
     L = oracle_mod.lib()
     sb = _sbox()
     xt = lambda v: ((v << 1) ^ (0x1b if v & 0x80 else 0)) & 255
@@ -236,10 +243,11 @@ def test_key_material(check, oracle_mod):
         r = int.from_bytes(key[48:], "little") & 0x0ffffffc0ffffffc0ffffffc0fffffff
         for i in range(65):
             limbs = t.many(5)
-            assert all(v < 1 << 27 for v in limbs) and val(limbs) == pow(r, i, P1305), i
+            # table rows are pmul's b operand: every limb below 2^26 (rcdc_p1305.h)
+            assert all(v < 1 << 26 for v in limbs) and val(limbs) == pow(r, i, P1305), i
         for j in range(32):
             limbs = t.many(5)
-            assert all(v < 1 << 27 for v in limbs) and val(limbs) == pow(r, 1 << j, P1305), j
+            assert all(v < 1 << 26 for v in limbs) and val(limbs) == pow(r, 1 << j, P1305), j
         assert t.many(256) == te
         assert t.done()
 

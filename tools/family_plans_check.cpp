@@ -7,6 +7,9 @@
 // Cases, as whitespace-separated tokens:
 //   keymat (BYTE)*64
 //     -> keymat (RK256)*60 (RK128)*44 (RPOW)*325 (R2J)*160 (TE)*256
+//   pmul   (A)*5 (B)*5   pnorm (A)*5   pfull (A)*5   pblock (W)*4 K   ptag (H)*5 SLO SHI
+//     the limb arithmetic of rcdc_p1305.h (tests/test_p1305_host.py)
+//     -> the 5 limbs of the result; ptag: the 16 tag bytes
 //   pack   RAW N_SRC OUT_LEN NBLOBS (TYPE LEN ULEN IN_OFF PAD)* NPACKS (BLOB0 NBLOBS OUT_OFF)*
 //     blob i: id byte j = (31 i + j) & 255, nonce byte j = (i + 3 j) & 255; pack p: header
 //     nonce byte j = (5 p + j + 1) & 255; d_in = 0x10000, source j = 0x1000000 (j + 1)
@@ -60,6 +63,51 @@ void do_keymat() {
     for (auto &r : K.r2j)
         for (uint32_t v : r) printf(" %u", v);
     for (uint32_t v : K.te) printf(" %u", v);
+    printf("\n");
+}
+
+// The limb arithmetic of rcdc_p1305.h, one call per case.
+p1305::P26 rd_limbs() {
+    p1305::P26 a;
+    for (uint32_t &v : a.h) v = rd<uint32_t>();
+    return a;
+}
+
+void print_limbs(const char *what, const p1305::P26 &a) {
+    printf("%s %u %u %u %u %u\n", what, a.h[0], a.h[1], a.h[2], a.h[3], a.h[4]);
+}
+
+void do_pmul() {
+    const p1305::P26 a = rd_limbs(), b = rd_limbs();
+    print_limbs("pmul", p1305::pmul(a, b.h));
+}
+
+void do_pnorm() {
+    p1305::P26 a = rd_limbs();
+    p1305::pnorm(a);
+    print_limbs("pnorm", a);
+}
+
+void do_pfull() {
+    p1305::P26 a = rd_limbs();
+    p1305::pfull(a);
+    print_limbs("pfull", a);
+}
+
+void do_pblock() {
+    uint32_t w[4];
+    for (uint32_t &v : w) v = rd<uint32_t>();
+    const uint32_t k = rd<uint32_t>();
+    print_limbs("pblock", p1305::pblock(w, k));
+}
+
+void do_ptag() {
+    const p1305::P26 h = rd_limbs();
+    const uint64_t slo = rd<uint64_t>(), shi = rd<uint64_t>();
+    uint8_t tag[16];
+    p1305::ptag(h, slo, shi, tag);
+    printf("ptag");
+    for (uint8_t b : tag) printf(" %u", b);
     printf("\n");
 }
 
@@ -265,6 +313,11 @@ int main() {
         else if (what == "zwin") do_zwin();
         else if (what == "zdx") do_zdx();
         else if (what == "place") do_place();
+        else if (what == "pmul") do_pmul();
+        else if (what == "pnorm") do_pnorm();
+        else if (what == "pfull") do_pfull();
+        else if (what == "pblock") do_pblock();
+        else if (what == "ptag") do_ptag();
         else {
             fprintf(stderr, "family_plans_check: unknown case '%s'\n", what.c_str());
             return 2;
