@@ -1152,6 +1152,113 @@ rcdc_status rcdc_prune_mark(rcdc_prune *pr, uint8_t *d_counts, uint8_t *d_used,
 rcdc_status rcdc_prune_keep(rcdc_prune *pr, const uint8_t *kinds, const uint32_t *file_rank,
                             uint8_t *d_keep, void *hip_stream);
 
+/* ---- tree blobs parsed on the device (blob/tree.rs, backend/node.rs) --------
+ * What find_used_blobs (commands/prune.rs:1582-1632) and TreeStreamerOnce
+ * (blob/tree.rs:618-800) read out of Tree { nodes: Vec<Node> }, for a batch
+ * of decoded tree blobs in HBM: n_blobs refs (off, len) into one arena d_text
+ * of text_len bytes, at any alignment.  No id and no byte of the text reaches
+ * the host.
+ *
+ * The device parses a strict grammar G_T and nothing else.  A blob outside
+ * G_T is no error: its status is RCDC_TRPARSE_NOT_PARSED, it adds nothing to
+ * any output, the numbering of the other blobs does not depend on it, and the
+ * caller parses it on the host.  G_T (whitespace as in rcdc_index_parse's G:
+ * space, \t, \n, \r between any two tokens and around the root; trailing
+ * bytes other than whitespace are outside G_T):
+ *   root  {"nodes": null | [node, ...]}   that key, once, and no other
+ *   node  an object; each key at most once, in any order, from this set:
+ *           name                                     string, required
+ *           type                                     required; "file", "dir",
+ *               "symlink", "dev", "chardev", "fifo" or "socket", literally
+ *           mode, uid, gid                           null | int <= 2^32 - 1
+ *           mtime, atime, ctime, user, group         null | string
+ *           inode, device_id, size, links, device    int <= 2^64 - 1
+ *           linktarget                               string; required when
+ *                                                    type is "symlink"
+ *           linktarget_raw                           null | string
+ *           content                                  null | [id, ...]
+ *           subtree                                  null | id
+ *           extended_attributes   [{"name": string, "value": null | string},
+ *                                  ...]  both keys at most once, name required
+ *         a "dir" node without a non-null subtree is outside G_T (the
+ *         reference unwraps it in find_used_blobs and reports it in
+ *         check_trees: that decision stays with the host path)
+ *   id      a string of exactly 64 hex digits, either case, no escapes
+ *   int     decimal digits, no sign / fraction / exponent / leading zero
+ *   string  a JSON string: no raw byte below 0x20; the escapes \" \\ \/ \b \f
+ *           \n \r \t \uXXXX, \uD800-\uDFFF excluded (serde's surrogate pairs
+ *           are not modelled); the raw bytes are well-formed UTF-8 (no
+ *           overlong form, no surrogate, at most U+10FFFF)
+ *   key     written literally: a key with a backslash is outside G_T
+ * Nesting is the grammar's own, 5 deep; anything deeper is outside G_T.  At
+ * a tile boundary of the structural pass a run of more than RCDC_TRPARSE_TILE
+ * backslashes before the boundary is outside G_T (the pass looks back over
+ * one tile at most to learn whether the tile's first byte is escaped).
+ *
+ * Where G_T is wider than the reference, and the whole list: mtime, atime and
+ * ctime (RusticTime), linktarget_raw and an attribute's value (base64) are
+ * checked as strings only; "device" is taken with every type.  A blob that
+ * is OK here and fails there fails in one of these texts, which carry no id.
+ *
+ * Output.  d_data_ids: the content ids of every node whose type is "file",
+ * 32 bytes each, in the order blob, node, array (the content of other types
+ * is validated and dropped, as find_used_blobs' match does).  d_tree_ids:
+ * the non-null subtree of every node of any type, in blob and node order
+ * (TreeStreamerOnce::next follows every node.subtree), and d_tree_is_dir one
+ * byte per such id: 1 where the node's type is "dir" (find_used_blobs
+ * inserts only those).  d_data_ids == NULL or d_tree_ids == NULL: those ids
+ * are counted, not written; d_tree_is_dir may be NULL on its own.  blobs
+ * (host, n_blobs records): status, the counts, and where the blob's ids
+ * start in each array.  result (host): the totals.
+ *
+ * Bound (rcdc_tree_parse_bound).  A content id is 66 bytes and every one but
+ * the last of an array is followed by a comma, so len bytes hold at most
+ * (len + 1) / 67 of them.  The smallest node with a subtree,
+ *   {"name":"","type":"dir","subtree":"<64>"}
+ * has 101 bytes ("dir" and "dev" are the shortest types), 102 with its
+ * comma: at most (len + 1) / 102 subtree ids.  The smallest node,
+ *   {"name":"","type":"dev"}
+ * has 24 bytes ("dir" needs a subtree), 25 with its comma: at most
+ * (len + 1) / 25 nodes.  cap_data_ids and cap_tree_ids (in ids; each checked
+ * only where its array is given) must be at least the sum of the bounds over
+ * the batch's blobs.
+ *
+ * refs, blobs and result are host memory; the work is queued on hip_stream
+ * and the call returns once it has drained.  RCDC_ERR_INVALID_INPUT before
+ * anything is launched: a null context, a null array with n_blobs > 0
+ * (d_data_ids, d_tree_ids and d_tree_is_dir may be null), a ref outside the
+ * arena, capacities below the bound, an id array that is not 16-byte
+ * aligned, a batch of 2^32 - 1 bytes or more.  n_blobs == 0 launches nothing.
+ *
+ * RCDC_TRPARSE_TILE: the structural pass works on tiles of this many bytes,
+ * counted from the 16-byte boundary at or before each blob's first byte.   */
+#define RCDC_TRPARSE_TILE       4096u
+#define RCDC_TRPARSE_OK         0u
+#define RCDC_TRPARSE_NOT_PARSED 1u
+typedef struct {
+    uint64_t off, len;
+} rcdc_trparse_ref; /* 16 B */
+typedef struct {
+    uint32_t status;     /* RCDC_TRPARSE_OK / RCDC_TRPARSE_NOT_PARSED */
+    uint32_t nodes;
+    uint32_t data_ids, tree_ids;
+    uint64_t data_start; /* its first id in d_data_ids                  */
+    uint64_t tree_start; /* its first id in d_tree_ids / d_tree_is_dir  */
+} rcdc_trparse_blob; /* 32 B */
+typedef struct {
+    uint64_t data_ids, tree_ids, nodes;
+    uint64_t blobs_not_parsed;
+} rcdc_trparse_result; /* 32 B */
+
+void rcdc_tree_parse_bound(uint64_t len, uint64_t *max_data_ids, uint64_t *max_tree_ids,
+                           uint64_t *max_nodes);
+uint32_t rcdc_tree_parse_tile(void); /* == RCDC_TRPARSE_TILE */
+rcdc_status rcdc_tree_parse(rcdc_ctx *ctx, const void *d_text, uint64_t text_len,
+                            const rcdc_trparse_ref *refs, uint32_t n_blobs, void *d_data_ids,
+                            uint64_t cap_data_ids, void *d_tree_ids, uint8_t *d_tree_is_dir,
+                            uint64_t cap_tree_ids, rcdc_trparse_blob *blobs,
+                            rcdc_trparse_result *result, void *hip_stream);
+
 /* Page-locked and device bytes currently held by all ingest engines of the
  * process (their own buffers, as rcdc_ingest_footprint counts them).        */
 void rcdc_ingest_mem_live(uint64_t *pinned_bytes, uint64_t *device_bytes);

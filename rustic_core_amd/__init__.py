@@ -23,6 +23,9 @@ from .prune import (  # noqa: F401
 from .index_write import (  # noqa: F401
     DeviceIndexer, FileRecord, PackRecord, WrittenJson, save_index_files, write_json,
 )
+from .tree import (  # noqa: F401
+    ParsedTrees, find_used_blobs, parse_tree_host, parse_trees, snapshot_trees,
+)
 
 __all__ = [
     "ErrorKind", "RusticError", "Chunker", "ChunkIter", "ConfigFile", "Context",
@@ -31,4 +34,5 @@ __all__ = [
     "BlobCopier", "CopyPackBlobs", "CopyStats", "NewPack", "plan_copy", "plan_repack",
     "LimitOption", "PackStatus", "PackToDo", "PrunePlan", "PruneOptions", "PruneStats",
     "DeviceIndexer", "FileRecord", "PackRecord", "WrittenJson", "save_index_files", "write_json",
+    "ParsedTrees", "find_used_blobs", "parse_tree_host", "parse_trees", "snapshot_trees",
 ]

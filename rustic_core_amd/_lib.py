@@ -47,6 +47,7 @@ EXPORTS = (
     "rcdc_prune_create", "rcdc_prune_destroy", "rcdc_prune_set_entries", "rcdc_prune_mark",
     "rcdc_prune_keep",
     "rcdc_index_write", "rcdc_index_write_bound", "rcdc_index_write_span",
+    "rcdc_tree_parse", "rcdc_tree_parse_bound", "rcdc_tree_parse_tile",
 )
 ABI_VERSION = 5
 
@@ -124,6 +125,12 @@ class IxwriteFile(ctypes.Structure):
 class IxwriteOut(ctypes.Structure):
     """rcdc_ixwrite_out."""
     _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64)]
+
+
+class TrparseResult(ctypes.Structure):
+    """rcdc_trparse_result."""
+    _fields_ = [("data_ids", ctypes.c_uint64), ("tree_ids", ctypes.c_uint64),
+                ("nodes", ctypes.c_uint64), ("blobs_not_parsed", ctypes.c_uint64)]
 
 
 class PruneResult(ctypes.Structure):
@@ -354,6 +361,12 @@ def lib() -> ctypes.CDLL:
     L.rcdc_index_write.restype = st
     L.rcdc_index_write.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, vp, u64, vp, u32,
                                    vp, u64, vp, u64, vp, u64, vp, P(u64), vp]
+    L.rcdc_tree_parse_bound.restype = None
+    L.rcdc_tree_parse_bound.argtypes = [u64, P(u64), P(u64), P(u64)]
+    L.rcdc_tree_parse_tile.restype = u32
+    L.rcdc_tree_parse_tile.argtypes = []
+    L.rcdc_tree_parse.restype = st
+    L.rcdc_tree_parse.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, u64, vp, vp, vp]
     _lib = L
     return L
 

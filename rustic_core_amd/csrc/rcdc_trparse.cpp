@@ -1,0 +1,153 @@
+// rcdc_tree_parse (include/rcdc.h): the host half -- argument checks, the
+// tile table, scratch memory and the order of the launches.  The kernels are
+// in rcdc_trparse.hip.
+//
+// The call stops the stream twice: once after the structural pass, to size
+// the record arrays from its four totals, and once at the end, to hand the
+// per-blob records to the caller.  Scratch lives for one call.
+
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "rcdc_host.h"
+#include "rcdc_trparse.h"
+
+using namespace rcdc;
+
+namespace {
+
+// device allocations of one call
+struct Scratch {
+    std::vector<void *> ptrs;
+    ~Scratch() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+    template <class T>
+    hipError_t get(T **out, uint64_t n) {
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, (n ? n : 1) * sizeof(T));
+        if (e == hipSuccess) ptrs.push_back(p);
+        *out = static_cast<T *>(p);
+        return e;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+void rcdc_tree_parse_bound(uint64_t len, uint64_t *max_data_ids, uint64_t *max_tree_ids,
+                           uint64_t *max_nodes) {
+    // n content ids and their commas: 67 n - 1 bytes; n nodes with a subtree:
+    // 102 n - 1; n nodes: 25 n - 1 (rcdc.h)
+    if (max_data_ids) *max_data_ids = (len + 1) / 67;
+    if (max_tree_ids) *max_tree_ids = (len + 1) / 102;
+    if (max_nodes) *max_nodes = (len + 1) / 25;
+}
+
+uint32_t rcdc_tree_parse_tile(void) { return RCDC_TRPARSE_TILE; }
+
+rcdc_status rcdc_tree_parse(rcdc_ctx *ctx, const void *d_text, uint64_t text_len,
+                            const rcdc_trparse_ref *refs, uint32_t n_blobs, void *d_data_ids,
+                            uint64_t cap_data_ids, void *d_tree_ids, uint8_t *d_tree_is_dir,
+                            uint64_t cap_tree_ids, rcdc_trparse_blob *blobs,
+                            rcdc_trparse_result *result, void *hip_stream) {
+    if (!ctx) return invalid("rcdc_tree_parse: ctx is NULL");
+    if (!result) return invalid("rcdc_tree_parse: result is NULL");
+    if (n_blobs && (!refs || !blobs)) return invalid("rcdc_tree_parse: null array");
+    uint64_t need_data = 0, need_tree = 0, n_tiles = 0, bytes = 0;
+    std::vector<uint32_t> tile_first(n_blobs + 1u, 0u);
+    const uint64_t mis = (uint64_t)(uintptr_t)d_text & 15u;
+    for (uint32_t b = 0; b < n_blobs; b++) {
+        const rcdc_trparse_ref r = refs[b];
+        if (r.off > text_len || r.len > text_len - r.off)
+            return invalid("rcdc_tree_parse: a ref lies outside the arena");
+        if (r.len && !d_text) return invalid("rcdc_tree_parse: d_text is NULL");
+        uint64_t d = 0, t = 0;
+        rcdc_tree_parse_bound(r.len, &d, &t, nullptr);
+        need_data += d;
+        need_tree += t;
+        bytes += r.len;
+        tile_first[b] = (uint32_t)n_tiles;
+        if (r.len) {
+            const uint64_t v0 = (r.off + mis) & ~15ull;
+            n_tiles += (r.off + mis + r.len - v0 + kTrTile - 1) / kTrTile;
+        }
+        // every count of the structural pass is a count of bytes
+        if (n_tiles >= 0xFFFFFFFFull || bytes >= 0xFFFFFFFFull)
+            return invalid("rcdc_tree_parse: the batch holds 2^32 - 1 bytes or more");
+    }
+    tile_first[n_blobs] = (uint32_t)n_tiles;
+    if ((d_data_ids && cap_data_ids < need_data) ||
+        ((d_tree_ids || d_tree_is_dir) && cap_tree_ids < need_tree))
+        return invalid("rcdc_tree_parse: capacities below rcdc_tree_parse_bound");
+    if (((uintptr_t)d_data_ids & 15u) || ((uintptr_t)d_tree_ids & 15u))
+        return invalid("rcdc_tree_parse: the id arrays must be 16-byte aligned");
+    *result = rcdc_trparse_result{};
+    if (n_blobs == 0) return RCDC_OK;
+
+    DeviceGuard g(ctx_device(ctx));
+    hipStream_t st = (hipStream_t)hip_stream;
+    Scratch sc;
+    TrArgs a = {};
+    a.text = static_cast<const uint8_t *>(d_text);
+    a.text_len = text_len;
+    a.n_blobs = n_blobs;
+    a.n_tiles = (uint32_t)n_tiles;
+    rcdc_trparse_ref *d_refs = nullptr;
+    uint32_t *d_tile_first = nullptr;
+    HIP_TRY(sc.get(&d_refs, n_blobs));
+    HIP_TRY(sc.get(&d_tile_first, n_blobs + 1ull));
+    HIP_TRY(sc.get(&a.sums, n_tiles));
+    HIP_TRY(sc.get(&a.ins, n_tiles));
+    HIP_TRY(sc.get(&a.esc, n_tiles));
+    HIP_TRY(sc.get(&a.counts, n_tiles + 1));
+    HIP_TRY(sc.get(&a.blob_ok, n_blobs));
+    HIP_TRY(sc.get(&a.blob_bad, n_blobs));
+    HIP_TRY(hipMemcpyAsync(d_refs, refs, n_blobs * sizeof *refs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_tile_first, tile_first.data(), (n_blobs + 1ull) * 4,
+                          hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(a.blob_bad, 0, n_blobs * 4ull, st));
+    a.refs = d_refs;
+    a.tile_first = d_tile_first;
+    HIP_TRY(launch_tr_structure(a, st));
+    HIP_TRY(hipMemcpyAsync(&a.total, a.counts + n_tiles, sizeof a.total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+
+    HIP_TRY(sc.get(&a.node_open, a.total.nodes));
+    HIP_TRY(sc.get(&a.id_open, a.total.ids));
+    HIP_TRY(sc.get(&a.c4, a.total.c4));
+    HIP_TRY(sc.get(&a.c2, a.total.c2));
+    HIP_TRY(sc.get(&a.tmp_ids, (uint64_t)a.total.ids * 32));
+    HIP_TRY(sc.get(&a.tmp_nodes, a.total.nodes));
+    uint32_t *adds = nullptr;
+    HIP_TRY(sc.get(&adds, ((uint64_t)a.total.nodes + 1) * 4));
+    a.adds = adds;
+    uint32_t *add_sums = nullptr;
+    HIP_TRY(sc.get(&add_sums, ((uint64_t)a.total.nodes / kTrScan + 2) * 4));
+    a.add_sums = add_sums;
+    HIP_TRY(sc.get(&a.blobs, n_blobs));
+    a.data_ids = static_cast<uint8_t *>(d_data_ids);
+    a.tree_ids = static_cast<uint8_t *>(d_tree_ids);
+    a.tree_is_dir = d_tree_is_dir;
+    // counted, not written: no capacity to hold the lanes to
+    a.cap_data_ids = d_data_ids ? cap_data_ids : ~0ull;
+    a.cap_tree_ids = (d_tree_ids || d_tree_is_dir) ? cap_tree_ids : ~0ull;
+    HIP_TRY(launch_tr_parse(a, st));
+    uint32_t tot[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(tot, adds + (uint64_t)a.total.nodes * 4, sizeof tot,
+                          hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(blobs, a.blobs, n_blobs * sizeof *blobs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tot[0] > a.cap_data_ids || tot[1] > a.cap_tree_ids)
+        return set_error(RCDC_ERR_INTERNAL, "rcdc_tree_parse: more output than the bound allows");
+    result->data_ids = tot[0];
+    result->tree_ids = tot[1];
+    result->nodes = tot[2];
+    for (uint32_t b = 0; b < n_blobs; b++)
+        result->blobs_not_parsed += blobs[b].status != RCDC_TRPARSE_OK;
+    return RCDC_OK;
+}
+
+}  // extern "C"

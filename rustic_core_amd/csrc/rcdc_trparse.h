@@ -1,0 +1,89 @@
+// rcdc_tree_parse: what the host half (rcdc_trparse.cpp) and the kernels
+// (rcdc_trparse.hip) share.  Included by those two units only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/rcdc.h"
+
+namespace rcdc {
+
+constexpr uint32_t kTrTile = RCDC_TRPARSE_TILE;  // bytes per tile: one wave, kTrRows rows
+constexpr uint32_t kTrRow = 64 * 16;             // one 16-byte load per lane
+constexpr uint32_t kTrRows = kTrTile / kTrRow;
+constexpr uint32_t kTrBlock = 256;               // 4 tiles per workgroup
+constexpr uint32_t kTrScan = 1024;               // node records per workgroup of the numbering's scan
+
+// A tile as a function of the string state at its first byte (whether that
+// byte is escaped is known before, TrArgs::esc): the parity of its quotes
+// that count, and the change of depth when it starts outside (d0) or inside
+// (d1) a string.
+struct TrTileSum {
+    int32_t d0, d1;
+    uint32_t q;
+};
+// The state at a tile's first byte.
+struct TrTileIn {
+    uint32_t instr;
+    int32_t depth;
+};
+// Per tile, then (after the scan) before the tile: node opens ('{' at depth
+// 2), string opens at depth 4 (the elements of "content"), ']' at depth 4
+// (closes "content" or "extended_attributes") and ']' at depth 2 (closes
+// "nodes").
+struct TrCounts {
+    uint32_t nodes, ids, c4, c2;
+};
+struct TrIdOpen {
+    uint64_t pos;
+    uint32_t blob, pad;
+};
+struct TrNodeOpen {
+    uint64_t pos;
+    uint32_t blob, id_rank, c4_rank, pad;
+};
+struct TrClose {
+    uint64_t pos;
+    uint32_t blob, rank;  // id opens (c4) / node opens (c2) before it
+};
+constexpr uint32_t kTrNodeOk = 1u, kTrNodeFile = 2u, kTrNodeDir = 4u, kTrNodeSubtree = 8u;
+struct TrNodeTmp {
+    uint32_t subtree[8];
+    uint32_t flags;     // kTrNode*
+    uint32_t blob;
+    uint32_t id0, nids; // its content: id opens [id0, id0 + nids)
+};
+
+struct TrArgs {
+    const uint8_t *text;
+    uint64_t text_len;
+    const rcdc_trparse_ref *refs;   // device copy
+    const uint32_t *tile_first;     // n_blobs + 1
+    uint32_t n_blobs, n_tiles;
+    // scratch
+    TrTileSum *sums;
+    TrTileIn *ins;
+    uint8_t *esc;                   // per tile: its first byte is escaped
+    TrCounts *counts;               // n_tiles + 1: the last one holds the totals
+    TrNodeOpen *node_open;
+    TrIdOpen *id_open;
+    TrClose *c4, *c2;
+    TrCounts total;
+    uint8_t *tmp_ids;               // 32 B per id open
+    TrNodeTmp *tmp_nodes;
+    uint32_t *blob_ok;              // the blob lane's verdict, then the blob's
+    uint32_t *blob_bad;             // set by any lane that fails
+    void *adds;                     // four uint32 per node open, + 1: the numbering's scan
+    void *add_sums;                 // four uint32 per kTrScan node opens, + 1
+    // outputs (device)
+    uint8_t *data_ids, *tree_ids, *tree_is_dir;
+    uint64_t cap_data_ids, cap_tree_ids;
+    rcdc_trparse_blob *blobs;
+};
+
+// the structural pass up to the totals in counts[n_tiles]
+hipError_t launch_tr_structure(const TrArgs &a, hipStream_t st);
+// the structural pass's emit, the strict lanes, the numbering
+hipError_t launch_tr_parse(const TrArgs &a, hipStream_t st);
+
+}  // namespace rcdc

@@ -13,8 +13,9 @@ order-dependent marking, the sums per pack and the first-wins pick -- runs on
 the device over entry arrays in HBM (``DevicePrune``); ``device=None`` runs
 the same rule in plain Python in the reference's sequential shape, which is
 what the device is tested against.  The per-pack part (thresholds, the
-candidate sort, one running sum) is host work either way.  Finding the used
-ids and deleting packs stay with the caller; ``index_updates`` is the loop
+candidate sort, one running sum) is host work either way.  The used ids come
+from ``tree.find_used_blobs`` as a device tensor; deleting packs stays with
+the caller; ``index_updates`` is the loop
 of ``do_prune`` that rebuilds the index (:1230-1353) as data, and
 ``write_index`` feeds it to an ``index_write.DeviceIndexer`` over the plan's
 own entry arrays, so the new index files are written on the device.
