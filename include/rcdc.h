@@ -1259,6 +1259,102 @@ rcdc_status rcdc_tree_parse(rcdc_ctx *ctx, const void *d_text, uint64_t text_len
                             uint64_t cap_tree_ids, rcdc_trparse_blob *blobs,
                             rcdc_trparse_result *result, void *hip_stream);
 
+/* ---- pack headers parsed on the device (repofile/packfile.rs) --------------
+ * What PackHeader::from_binary (packfile.rs:88-242) reads out of the table at
+ * the end of a pack, for a batch of opened (plaintext) headers in HBM:
+ * n_headers refs (off, len) into one arena d_plain of plain_len bytes, at any
+ * alignment.  The output is what IndexCollector keeps of the packs, in the
+ * layout of rcdc_index_parse, so it goes the same way to rcdc_dindex_add and
+ * rcdc_index_write as device pointers; no entry and no id reaches the host.
+ *
+ * The format.  Entries follow each other from byte 0; integers are little
+ * endian:
+ *   type byte 0 (data), 1 (tree)   37 bytes: u32 length, id[32]
+ *   type byte 2 (data), 3 (tree)   41 bytes: u32 length,
+ *                                  u32 uncompressed_length, id[32]
+ * The blob type is type & 1, the offset of an entry the sum of the lengths
+ * before it, and an uncompressed length of 0 in a 41-byte entry is kept as 0
+ * (NonZeroU32::new gives None).
+ *
+ * Status per header:
+ *   RCDC_PKHDR_OK
+ *   RCDC_PKHDR_BAD_TYPE   a type byte above 3 at an entry start (checked
+ *                         before the entry's size)
+ *   RCDC_PKHDR_CUT_SHORT  the last entry has fewer bytes than its size
+ *   RCDC_PKHDR_OVERFLOW   neither of those, and the running offset after some
+ *                         entry, the last included, exceeds 2^32 - 1 (the
+ *                         reference's offset += length is a u32 add)
+ * A header whose status is not OK is no error of the call: it adds nothing
+ * to any output and the numbering of the other headers does not depend on
+ * it; of its record only status, err_entry and err_pos (BAD_TYPE and
+ * CUT_SHORT: the offending entry's index and its byte position in the
+ * header) are set, the rest is 0.  len == 0 is OK: an empty pack, type data.
+ *
+ * Output, the collector's rule as in rcdc_index_parse: a header goes to the
+ * type of its first entry (an empty one to data), gets the next pack number
+ * of that type counted from pack_base[type] (only OK headers count), and all
+ * its entries become entries of that type in order: d_ids[type] gets
+ * 32 bytes per entry, d_locs[type] one {pack number, offset, length,
+ * uncompressed_length or 0}.  d_ids[t] == NULL: entries of type t are
+ * counted, not written; d_locs[t] == NULL: only the ids are written.
+ * headers (host, n_headers records): status, type and number, the first
+ * entry in the type's arrays and the count, how many of the entries are data
+ * and how many tree (a header with both is mixed: its entries are written
+ * under the first one's type all the same, and the caller decides),
+ * PackHeaderRef::size() = 32 + the entries' bytes and
+ * PackHeaderRef::pack_size() = 36 + sum(length + entry bytes)
+ * (packfile.rs:355-372).  result (host): the totals.
+ *
+ * Bound (rcdc_pack_header_parse_bound): an entry has at least 37 bytes, so
+ * len bytes hold at most len / 37.  cap_entries (the capacity of each of
+ * d_ids[t] and d_locs[t], in entries) must be at least the sum of the bounds
+ * over the batch's headers.
+ *
+ * refs, headers, pack_base and result are host memory; the work is queued on
+ * hip_stream and the call returns once it has drained.
+ * RCDC_ERR_INVALID_INPUT before anything is launched: a null context, a null
+ * array with n_headers > 0 (d_ids / d_locs entries may be null), a ref
+ * outside the arena, a capacity below the bound, an entry array that is not
+ * 16-byte aligned, a bound of 2^32 - 1 entries or more.  n_headers == 0
+ * launches nothing.
+ *
+ * RCDC_PKHDR_TILE: the passes work on tiles of this many bytes, counted from
+ * the 16-byte boundary at or before each header's first byte.               */
+#define RCDC_PKHDR_TILE      2048u
+#define RCDC_PKHDR_OK        0u
+#define RCDC_PKHDR_BAD_TYPE  1u
+#define RCDC_PKHDR_CUT_SHORT 2u
+#define RCDC_PKHDR_OVERFLOW  3u
+typedef struct {
+    uint64_t off, len;
+} rcdc_pkhdr_ref; /* 16 B */
+typedef struct {
+    uint32_t status;     /* RCDC_PKHDR_*                                   */
+    uint32_t type;       /* of its first entry; 0 for an empty header      */
+    uint32_t number;     /* its pack number in that type                   */
+    uint32_t count;      /* entries                                        */
+    uint64_t first;      /* its first entry in d_ids[type] / d_locs[type]  */
+    uint32_t data, tree; /* entries of each blob type: both != 0 is mixed  */
+    uint64_t size;       /* PackHeaderRef::size()                          */
+    uint64_t pack_size;  /* PackHeaderRef::pack_size()                     */
+    uint64_t err_pos;    /* BAD_TYPE / CUT_SHORT: the entry's first byte   */
+    uint32_t err_entry;  /* and its index                                  */
+    uint32_t pad;
+} rcdc_pkhdr_header; /* 64 B */
+typedef struct {
+    uint64_t packs[2], entries[2];
+    uint64_t headers_not_parsed;
+} rcdc_pkhdr_result; /* 40 B */
+
+uint64_t rcdc_pack_header_parse_bound(uint64_t len); /* len / 37 */
+uint32_t rcdc_pack_header_parse_tile(void);          /* == RCDC_PKHDR_TILE */
+rcdc_status rcdc_pack_header_parse(rcdc_ctx *ctx, const void *d_plain, uint64_t plain_len,
+                                   const rcdc_pkhdr_ref *refs, uint32_t n_headers,
+                                   const uint32_t pack_base[2], void *const d_ids[2],
+                                   rcdc_dindex_loc *const d_locs[2], uint64_t cap_entries,
+                                   rcdc_pkhdr_header *headers, rcdc_pkhdr_result *result,
+                                   void *hip_stream);
+
 /* Page-locked and device bytes currently held by all ingest engines of the
  * process (their own buffers, as rcdc_ingest_footprint counts them).        */
 void rcdc_ingest_mem_live(uint64_t *pinned_bytes, uint64_t *device_bytes);

@@ -26,6 +26,10 @@ from .index_write import (  # noqa: F401
 from .tree import (  # noqa: F401
     ParsedTrees, find_used_blobs, parse_tree_host, parse_trees, snapshot_trees,
 )
+from .headers import (  # noqa: F401
+    HeaderResult, PackChecker, ParsedHeaders, RepairReport, index_checked, parse_headers,
+    read_headers, repair_index,
+)
 
 __all__ = [
     "ErrorKind", "RusticError", "Chunker", "ChunkIter", "ConfigFile", "Context",
@@ -35,4 +39,6 @@ __all__ = [
     "LimitOption", "PackStatus", "PackToDo", "PrunePlan", "PruneOptions", "PruneStats",
     "DeviceIndexer", "FileRecord", "PackRecord", "WrittenJson", "save_index_files", "write_json",
     "ParsedTrees", "find_used_blobs", "parse_tree_host", "parse_trees", "snapshot_trees",
+    "HeaderResult", "PackChecker", "ParsedHeaders", "RepairReport", "index_checked",
+    "parse_headers", "read_headers", "repair_index",
 ]

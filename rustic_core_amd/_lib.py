@@ -48,6 +48,7 @@ EXPORTS = (
     "rcdc_prune_keep",
     "rcdc_index_write", "rcdc_index_write_bound", "rcdc_index_write_span",
     "rcdc_tree_parse", "rcdc_tree_parse_bound", "rcdc_tree_parse_tile",
+    "rcdc_pack_header_parse", "rcdc_pack_header_parse_bound", "rcdc_pack_header_parse_tile",
 )
 ABI_VERSION = 5
 
@@ -131,6 +132,12 @@ class TrparseResult(ctypes.Structure):
     """rcdc_trparse_result."""
     _fields_ = [("data_ids", ctypes.c_uint64), ("tree_ids", ctypes.c_uint64),
                 ("nodes", ctypes.c_uint64), ("blobs_not_parsed", ctypes.c_uint64)]
+
+
+class PkhdrResult(ctypes.Structure):
+    """rcdc_pkhdr_result."""
+    _fields_ = [("packs", ctypes.c_uint64 * 2), ("entries", ctypes.c_uint64 * 2),
+                ("headers_not_parsed", ctypes.c_uint64)]
 
 
 class PruneResult(ctypes.Structure):
@@ -367,6 +374,12 @@ def lib() -> ctypes.CDLL:
     L.rcdc_tree_parse_tile.argtypes = []
     L.rcdc_tree_parse.restype = st
     L.rcdc_tree_parse.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, u64, vp, vp, vp]
+    L.rcdc_pack_header_parse_bound.restype = u64
+    L.rcdc_pack_header_parse_bound.argtypes = [u64]
+    L.rcdc_pack_header_parse_tile.restype = u32
+    L.rcdc_pack_header_parse_tile.argtypes = []
+    L.rcdc_pack_header_parse.restype = st
+    L.rcdc_pack_header_parse.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, u64, vp, vp, vp]
     _lib = L
     return L
 

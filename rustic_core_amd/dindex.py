@@ -17,7 +17,9 @@ of index files that is already in HBM and has the device parse it
 (rcdc_index_parse: a strict grammar, a file outside it goes through
 ``IndexFile.from_json`` on the host), and ``load`` is ``decrypt_file``
 (backend/decrypt.rs:421-439) for a batch of sealed index files in front of
-that.
+that.  ``extend_headers`` takes opened pack headers in HBM (rcdc_pack_header_
+parse): what ``headers.index_checked`` adds for packs the index files have
+wrong or lack.
 """
 from __future__ import annotations
 
@@ -395,6 +397,66 @@ class DeviceIndex:
                     self._add(t, res.ids[tpe][a:b], locs, DEVICE_PTRS)
             i = j
         return res.files["status"].copy()
+
+    def extend_headers(self, d_plain, offs, lens, pack_ids) -> np.ndarray:
+        """``extend`` for packs whose opened headers are in HBM: header i is
+        ``d_plain[offs[i] : offs[i] + lens[i]]`` (a uint8 device tensor) and
+        belongs to pack ``pack_ids[i]``.  The batch is parsed on the device
+        (rcdc_pack_header_parse) and its arrays go to rcdc_dindex_add as
+        device pointers; the pack ids and ``pack_size()`` are recorded per
+        type.  Returns the per-header records (``headers.PK_HEADER``).
+
+        A header that failed (status not OK) or is mixed (blobs of both
+        types) is not added and is left to the caller, by its record.
+        Consecutive added headers form a run, added with one device add per
+        type; the parse has numbered a mixed header as a pack of its first
+        blob's type, so the pack numbers of the runs after it are shifted
+        down, as ``extend_json`` shifts them up for the files of the host.
+        So pack numbers, entry numbers and sizes are those of ``extend``
+        over the added packs in order."""
+        from .headers import OK, parse_headers
+        pack_ids = [bytes(i) for i in pack_ids]
+        if len(pack_ids) != len(lens):
+            raise RusticError(ErrorKind.InvalidInput, "one pack id per header")
+        base = {t: len(self._t[t].packs) for t in (DATA, TREE)}  # what the parse counts from
+        with self._stage("parse"):
+            res = parse_headers(d_plain, offs, lens, (base[DATA], base[TREE]), device=self.device,
+                                want_ids=(self._t[DATA].mode != "none", True),
+                                want_locs=(self._t[DATA].mode == "full", True))
+        h = res.headers
+        good = (h["status"] == OK) & ~((h["data"] != 0) & (h["tree"] != 0))
+        skipped = {DATA: 0, TREE: 0}  # mixed headers the parse has numbered so far
+        i, n = 0, len(h)
+        while i < n:
+            if not good[i]:
+                if h["status"][i] == OK:
+                    skipped[int(h["type"][i])] += 1
+                i += 1
+                continue
+            j = i
+            while j < n and good[j]:
+                j += 1
+            run = h[i:j]
+            for k in range(i, j):
+                t = self._t[int(h["type"][k])]
+                t.packs.append(pack_ids[k])
+                t.total_size += int(h["pack_size"][k])
+            for tpe in (DATA, TREE):
+                t = self._t[tpe]
+                sel = run[run["type"] == tpe]
+                ne = int(sel["count"].sum())
+                if not ne or t.mode == "none":
+                    continue
+                a = int(sel["first"][0])  # a type's entries follow each other in header order
+                locs = None
+                if t.mode == "full":
+                    locs = res.locs[tpe][a:a + ne]
+                    if skipped[tpe]:
+                        locs[:, 0] -= skipped[tpe]
+                with self._stage("add"):
+                    self._add(t, res.ids[tpe][a:a + ne], locs, DEVICE_PTRS)
+            i = j
+        return h.copy()
 
     def load(self, key, sealed_files) -> np.ndarray:
         """``decrypt_file`` (backend/decrypt.rs:421-439) for a batch of
