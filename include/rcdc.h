@@ -1355,6 +1355,134 @@ rcdc_status rcdc_pack_header_parse(rcdc_ctx *ctx, const void *d_plain, uint64_t 
                                    rcdc_pkhdr_header *headers, rcdc_pkhdr_result *result,
                                    void *hip_stream);
 
+/* ---- check's index pass and header compare on the device (commands/check.rs) -
+ * What check_packs does per pack with the blobs an index lists for it
+ * (check.rs:484-507) and what check_pack compares with the pack's own header
+ * (check.rs:779-786), for a batch of packs whose index entries are in HBM.
+ *
+ * Entries (device), by strides in bytes exactly as rcdc_prune_set_entries
+ * takes them: entry e has its 32 id bytes at d_ids + e * id_stride and its
+ * offset, length and uncompressed length (uint32 each, 0 for none) at
+ * d_off + e * off_stride, d_len + e * len_stride, d_ulen + e * ulen_stride,
+ * so the d_ids / d_locs arrays of rcdc_index_parse and of
+ * rcdc_pack_header_parse pass as they are (&d_locs->offset, ->length,
+ * ->uncompressed_length with stride 16; such records on a 16-byte boundary
+ * are read with one 16-byte load each, ids with stride 32 on a 16-byte
+ * boundary with two).  d_types: one byte per entry (0 data, 1 tree), or NULL:
+ * every entry has its pack's type, which is then the header's where a header
+ * is given and data otherwise.  ranges[p] = {first entry, count} is pack p;
+ * ranges may lie anywhere in the arrays and must not overlap; count is any
+ * uint32 (check has no 65 535 cap).  The arrays are read, never copied to the
+ * host.
+ *
+ * The header side, optional (hdrs == NULL: none): d_hdr_ids[t] / d_hdr_locs[t]
+ * are the outputs of rcdc_pack_header_parse, hdr_entries[t] the entries
+ * written to each, and hdrs[p] = {type, count, first} is taken from the
+ * rcdc_pkhdr_header record of pack p's header: its entries are the rows
+ * [first, first + count) of type's arrays and all have that type (a mixed
+ * header is the caller's).  type == RCDC_CKPACK_NO_HEADER: nothing to compare
+ * for this pack.
+ *
+ * The rule per pack.  Its type is its first entry's IN INPUT ORDER
+ * (blob_type() is read before the sort; an empty pack is data).  Its entries
+ * are put in the order of (offset, length, uncompressed_length) -- IndexBlob's
+ * cmp is BlobLocation's derived order; id and type take no part in it.
+ * Entries with equal locations keep their input order: the reference's
+ * sort_unstable leaves that open, so in an index that lists two blobs at one
+ * place, and only there, which blob_id a finding names may differ from the
+ * reference's.  Then with expected = 0, per entry in that order: a TYPE
+ * finding where its type is not the pack's, an OFFSET finding where its
+ * offset is not expected, and expected += length as a wrapping uint32 add
+ * (what a release build of the reference does; a debug build panics there).
+ *
+ * A pack whose entries are already non-decreasing needs no sort and is taken
+ * at any count.  One out of order is sorted in LDS up to
+ * RCDC_CKPACK_SORT_MAX entries.  Above that its status is RCDC_CKPACK_HOST:
+ * it adds nothing to any output (of its record only status and type are set),
+ * the numbering of the other packs' findings does not depend on it, and the
+ * caller applies the rule on the host.
+ *
+ * Output.  packs (host, n_packs records): status, type, the two finding
+ * counts, the end offset (expected after the last entry), header_len = 32 +
+ * sum(41 with an uncompressed length, else 37), which is
+ * PackHeaderRef::from_index_pack(..).size() as u64, the header verdict
+ * (NOT_COMPARED, EQUAL, DIFFERS), the first sorted position at which the two
+ * sides differ (the shorter count when one side is a prefix of the other;
+ * 0 unless DIFFERS) and where the pack's findings start.  EQUAL holds exactly
+ * when the counts agree and at every sorted position the id (all 32 bytes),
+ * offset, length, uncompressed length (0 and none the same) and the entry's
+ * type and the header's agree.  d_findings (device, cap_findings records, may
+ * be NULL with cap_findings 0): {pack, entry (its index in the arrays), kind,
+ * got, expected} -- TYPE: the entry's and the pack's type, OFFSET: the
+ * entry's and the expected offset -- in the reference's order: pack, sorted
+ * position, TYPE before OFFSET.  Counted, scanned, then written: the order
+ * does not depend on timing.  Records past cap_findings are not written; the
+ * counts and result->findings are right all the same.  d_order (device, n
+ * uint32, or NULL): d_order[first + k] is the entry at sorted position k of
+ * the pack that starts at first; rows outside every OK pack are not written.
+ *
+ * One launch over the packs (judge and count, a workgroup per pack), then
+ * sort and emit, each over a scanned list of the packs it has work for (those
+ * out of order; those with findings, a header or the order to write) with a
+ * grid that does not grow with the packs, and one scan of the counts.  No
+ * kernel waits for a value another lane has yet to write.  ranges, hdrs, hdr_entries, packs and result are
+ * host memory; the work is queued on hip_stream and the call returns once it
+ * has drained.  Calls on one context take turns.
+ *
+ * RCDC_ERR_INVALID_INPUT before anything is launched: a null context or
+ * result, a null array with a non-zero count (d_types, d_findings, d_order
+ * and hdrs may be null), n >= 2^32 - 1, a stride smaller than its element,
+ * offset / length arrays or strides that are not 4-byte aligned, a range past
+ * n, overlapping ranges, a header type above 1 that is not the marker, a
+ * header range past hdr_entries, a header array that is not 16-byte aligned.
+ * n_packs == 0 launches nothing.                                           */
+#define RCDC_CKPACK_SORT_MAX     4096u  /* 16 B of key and index each: 64 KiB of LDS */
+#define RCDC_CKPACK_OK           0u
+#define RCDC_CKPACK_HOST         1u
+#define RCDC_CKPACK_NOT_COMPARED 0u
+#define RCDC_CKPACK_EQUAL        1u
+#define RCDC_CKPACK_DIFFERS      2u
+#define RCDC_CKPACK_TYPE         0u     /* finding kinds */
+#define RCDC_CKPACK_OFFSET       1u
+#define RCDC_CKPACK_NO_HEADER    0xFFFFFFFFu
+typedef struct {
+    uint32_t type;  /* 0, 1 or RCDC_CKPACK_NO_HEADER */
+    uint32_t count;
+    uint64_t first; /* in d_hdr_ids[type] / d_hdr_locs[type] */
+} rcdc_ckpack_hdr; /* 16 B */
+typedef struct {
+    uint32_t status;          /* RCDC_CKPACK_OK / _HOST            */
+    uint32_t type;            /* of the first entry in input order */
+    uint32_t type_findings, offset_findings;
+    uint32_t end_offset;
+    uint32_t header_verdict;  /* NOT_COMPARED / EQUAL / DIFFERS    */
+    uint32_t header_diff;     /* first differing sorted position   */
+    uint32_t sorted;          /* 1: the entries were in order      */
+    uint64_t header_len;
+    uint64_t first_finding;   /* in d_findings                     */
+} rcdc_ckpack_pack; /* 48 B */
+typedef struct {
+    uint32_t pack, entry, kind, got, expected;
+} rcdc_ckpack_finding; /* 20 B */
+typedef struct {
+    uint64_t findings;    /* of all OK packs, written or not */
+    uint64_t packs_host;  /* packs with status HOST          */
+    uint64_t packs_sorted_on_device;
+} rcdc_ckpack_result; /* 24 B */
+
+uint32_t rcdc_check_packs_sort_max(void); /* == RCDC_CKPACK_SORT_MAX */
+rcdc_status rcdc_check_packs(rcdc_ctx *ctx, const void *d_ids, uint64_t id_stride,
+                             const void *d_off, uint64_t off_stride, const void *d_len,
+                             uint64_t len_stride, const void *d_ulen, uint64_t ulen_stride,
+                             const uint8_t *d_types, uint64_t n,
+                             const rcdc_prune_range *ranges, uint64_t n_packs,
+                             const void *const d_hdr_ids[2],
+                             const rcdc_dindex_loc *const d_hdr_locs[2],
+                             const uint64_t hdr_entries[2], const rcdc_ckpack_hdr *hdrs,
+                             rcdc_ckpack_pack *packs, rcdc_ckpack_finding *d_findings,
+                             uint64_t cap_findings, uint32_t *d_order,
+                             rcdc_ckpack_result *result, void *hip_stream);
+
 /* Page-locked and device bytes currently held by all ingest engines of the
  * process (their own buffers, as rcdc_ingest_footprint counts them).        */
 void rcdc_ingest_mem_live(uint64_t *pinned_bytes, uint64_t *device_bytes);

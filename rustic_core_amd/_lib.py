@@ -49,6 +49,7 @@ EXPORTS = (
     "rcdc_index_write", "rcdc_index_write_bound", "rcdc_index_write_span",
     "rcdc_tree_parse", "rcdc_tree_parse_bound", "rcdc_tree_parse_tile",
     "rcdc_pack_header_parse", "rcdc_pack_header_parse_bound", "rcdc_pack_header_parse_tile",
+    "rcdc_check_packs", "rcdc_check_packs_sort_max",
 )
 ABI_VERSION = 5
 
@@ -138,6 +139,12 @@ class PkhdrResult(ctypes.Structure):
     """rcdc_pkhdr_result."""
     _fields_ = [("packs", ctypes.c_uint64 * 2), ("entries", ctypes.c_uint64 * 2),
                 ("headers_not_parsed", ctypes.c_uint64)]
+
+
+class CkpackResult(ctypes.Structure):
+    """rcdc_ckpack_result."""
+    _fields_ = [("findings", ctypes.c_uint64), ("packs_host", ctypes.c_uint64),
+                ("packs_sorted_on_device", ctypes.c_uint64)]
 
 
 class PruneResult(ctypes.Structure):
@@ -380,6 +387,11 @@ def lib() -> ctypes.CDLL:
     L.rcdc_pack_header_parse_tile.argtypes = []
     L.rcdc_pack_header_parse.restype = st
     L.rcdc_pack_header_parse.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, u64, vp, vp, vp]
+    L.rcdc_check_packs_sort_max.restype = u32
+    L.rcdc_check_packs_sort_max.argtypes = []
+    L.rcdc_check_packs.restype = st
+    L.rcdc_check_packs.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64,
+                                   vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
     _lib = L
     return L
 

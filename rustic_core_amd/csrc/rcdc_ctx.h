@@ -1,7 +1,7 @@
 // rcdc_ctx.h -- the context, and what the units that work on it share:
 // rcdc_runtime.cpp (chunking, lanes, streams; it defines the helpers below)
 // and one unit per kernel family (rcdc_aead.cpp, rcdc_zstd_host.cpp,
-// rcdc_place.cpp).  Each family keeps its lock, scratch, events and
+// rcdc_place.cpp, rcdc_ckpack.cpp).  Each family keeps its lock, scratch, events and
 // page-locked memory in one member struct, which frees what it owns; the
 // other units (ingest, dindex, ixparse, prune) see the context only through
 // the narrow exports of rcdc_host.h.
@@ -94,6 +94,18 @@ struct PlaceState {
     }
 };
 
+// check's index pass (rcdc_check_packs): calls on one context take turns
+struct CkpackState {
+    std::mutex mu;
+    DevBuf<rcdc_prune_range> d_ranges;
+    DevBuf<rcdc_ckpack_hdr> d_hdrs;
+    DevBuf<rcdc_ckpack_pack> d_packs;
+    DevBuf<uint32_t> d_prefix;
+    DevBuf<uint32_t> d_order;  // of the packs sorted on the device
+    DevBuf<uint32_t> d_list, d_list_n;  // the packs the sort and emit passes have work for
+    DevBuf<uint64_t> d_totals;
+};
+
 }  // namespace rcdc
 
 // Destroyed by rcdc_ctx_destroy with its device current and its stream idle:
@@ -125,6 +137,7 @@ struct rcdc_ctx {
     rcdc::ZckState zck;
     rcdc::ZdxState zdx;
     rcdc::PlaceState place;
+    rcdc::CkpackState ckpack;
 };
 
 namespace rcdc {

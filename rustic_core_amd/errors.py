@@ -16,6 +16,7 @@ class ErrorKind(enum.Enum):
     InputOutput = "InputOutput"      # rabin.rs:131-138,174-180 (reader errors)
     Cryptography = "Cryptography"    # crypto/aespoly1305.rs:89-108 (MAC check)
     Verification = "Verification"    # backend/decrypt.rs:516-526 (extra_verify)
+    Repository = "Repository"        # commands/check.rs:962-974 (check found errors)
 
 
 class RusticError(Exception):

@@ -22,7 +22,7 @@ from __future__ import annotations
 import ctypes
 import hashlib
 import json
-from typing import Callable, Iterable, List, Optional, Sequence, Tuple
+from typing import Callable, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -149,6 +149,66 @@ def _id(x) -> bytes:
 def _uint(x, bits: int) -> None:
     if isinstance(x, bool) or not isinstance(x, int) or not 0 <= x < (1 << bits):
         raise ValueError(f"not a u{bits}")
+
+
+class TreeNode(NamedTuple):
+    """What check_trees (commands/check.rs:627-700) reads of a node."""
+    name: str
+    type: str                       # one of NODE_TYPES
+    content: Optional[List[bytes]]  # None: the node has no content
+    subtree: Optional[bytes]
+
+
+def parse_tree_nodes_host(text: bytes) -> List[TreeNode]:
+    """The nodes of one tree blob by ``parse_tree_host``'s rule, in order,
+    with their names: what ``check.check_trees`` judges.  A dir node without
+    a subtree is returned with ``subtree=None`` (check reports it as
+    NoSubTree; ``parse_tree_host`` raises there); everything else that does
+    not parse raises as it does there."""
+    try:
+        root = json.loads(bytes(text).decode("utf-8"), object_pairs_hook=_pairs)
+        if not isinstance(root, dict) or "nodes" not in root:
+            raise ValueError("missing field `nodes`")
+        nodes = root["nodes"] if root["nodes"] is not None else []
+        if not isinstance(nodes, list):
+            raise ValueError("nodes is no sequence")
+        out = []
+        for n in nodes:
+            _check_node(n)
+            content = n.get("content")
+            out.append(TreeNode(n["name"], n["type"],
+                                None if content is None else [_id(i) for i in content],
+                                None if n.get("subtree") is None else _id(n["subtree"])))
+        return out
+    except (ValueError, TypeError, RecursionError) as e:
+        raise _fail(str(e)) from e
+
+
+def _check_node(n) -> None:
+    """Node's deserialiser but for ``content`` and ``subtree``."""
+    if not isinstance(n, dict) or not isinstance(n.get("name"), str):
+        raise ValueError("a node is a map with a name")
+    tpe = n.get("type")
+    if tpe not in NODE_TYPES:
+        raise ValueError(f"unknown variant `{tpe}`")
+    if tpe == "symlink" and not isinstance(n.get("linktarget"), str):
+        raise ValueError("missing field `linktarget`")
+    for k in _U32:
+        if n.get(k) is not None:
+            _uint(n[k], 32)
+    for k in _STRINGS + ("linktarget_raw",):
+        if n.get(k) is not None and not isinstance(n[k], str):
+            raise ValueError(f"{k} is no string")
+    for k in _U64 + ("device",):
+        if k in n:
+            _uint(n[k], 64)
+    for x in n.get("extended_attributes", []):
+        if not isinstance(x, dict) or not isinstance(x.get("name"), str) or \
+                not isinstance(x.get("value"), (str, type(None))):
+            raise ValueError("extended attribute")
+    content = n.get("content")
+    if content is not None and not isinstance(content, list):
+        raise ValueError("content is no sequence")
 
 
 def parse_tree_host(text: bytes):
