@@ -1259,6 +1259,141 @@ rcdc_status rcdc_tree_parse(rcdc_ctx *ctx, const void *d_text, uint64_t text_len
                             uint64_t cap_tree_ids, rcdc_trparse_blob *blobs,
                             rcdc_trparse_result *result, void *hip_stream);
 
+/* ---- node records of tree blobs (commands/check.rs:627-700) ------------------
+ * rcdc_tree_nodes is rcdc_tree_parse -- the same kernels, the same three id
+ * outputs with the same meaning -- plus one fixed-size record per node: what
+ * check_trees judges of a node, and what ls, find and diff read of a tree.
+ *
+ * Grammar G_N.  G_T with one rule dropped: a "dir" node whose subtree is
+ * absent or null is inside G_N (check reports it as NoSubTree; it adds no
+ * entry to d_tree_ids).  Everything else is G_T's, every place where G_T is
+ * wider or narrower than the reference included.
+ *
+ * d_nodes: one rcdc_trnode per node of every OK blob, in blob and node order;
+ * a NOT_PARSED blob adds none and the numbering of the others does not depend
+ * on it.  The record:
+ *   name_off, name_len  the raw name: the arena offset of the first byte
+ *                       after its opening quote and the bytes up to its
+ *                       closing quote, escapes unresolved
+ *   blob                the index of the node's blob in refs
+ *   data_start          the count of d_data_ids entries before this node (the
+ *                       node's first content id where its type is "file";
+ *                       the content of other types is not in d_data_ids)
+ *   n_content           ids in "content" where it is an array, else 0
+ *   tree_index          the count of d_tree_ids entries before this node: the
+ *                       node's own entry where RCDC_TRNODE_SUBTREE is set
+ *   type                the index in file, dir, symlink, dev, chardev, fifo,
+ *                       socket
+ *   flags               RCDC_TRNODE_CONTENT: "content" is an array (of
+ *                       n_content ids, 0 for []); clear: absent or null.
+ *                       RCDC_TRNODE_SUBTREE: "subtree" is an id; clear: absent
+ *                       or null.  RCDC_TRNODE_NAME_ESC: the raw name holds a
+ *                       backslash.
+ * blobs: rcdc_trparse_blob's fields and node_start, the blob's first record.
+ *
+ * Bound: rcdc_tree_nodes_bound is rcdc_tree_parse_bound; the smallest node of
+ * G_N has 24 bytes as that of G_T has, so cap_nodes (in records) must be at
+ * least the sum of (len + 1) / 25 over the batch.  Refused before anything is
+ * launched: what rcdc_tree_parse refuses, a null d_nodes with n_blobs > 0,
+ * cap_nodes below the bound, a d_nodes that is not 16-byte aligned.          */
+#define RCDC_TRNODE_CONTENT  1u
+#define RCDC_TRNODE_SUBTREE  2u
+#define RCDC_TRNODE_NAME_ESC 4u
+typedef struct {
+    uint64_t name_off;
+    uint32_t name_len;
+    uint32_t blob;
+    uint32_t data_start;
+    uint32_t n_content;
+    uint32_t tree_index;
+    uint8_t type;
+    uint8_t flags; /* RCDC_TRNODE_* */
+    uint16_t pad;
+} rcdc_trnode; /* 32 B */
+typedef struct {
+    uint32_t status;     /* RCDC_TRPARSE_OK / RCDC_TRPARSE_NOT_PARSED */
+    uint32_t nodes;
+    uint32_t data_ids, tree_ids;
+    uint64_t data_start, tree_start;
+    uint64_t node_start; /* its first record in d_nodes */
+} rcdc_trnodes_blob; /* 40 B */
+
+void rcdc_tree_nodes_bound(uint64_t len, uint64_t *max_data_ids, uint64_t *max_tree_ids,
+                           uint64_t *max_nodes);
+rcdc_status rcdc_tree_nodes(rcdc_ctx *ctx, const void *d_text, uint64_t text_len,
+                            const rcdc_trparse_ref *refs, uint32_t n_blobs, void *d_data_ids,
+                            uint64_t cap_data_ids, void *d_tree_ids, uint8_t *d_tree_is_dir,
+                            uint64_t cap_tree_ids, rcdc_trnode *d_nodes, uint64_t cap_nodes,
+                            rcdc_trnodes_blob *blobs, rcdc_trparse_result *result,
+                            void *hip_stream);
+
+/* Raw names gathered: for each of the n node indices in d_index (device,
+ * uint32, any order, repeats allowed) the name_len raw bytes of that record's
+ * name are copied from the arena into d_names, back to back in list order.
+ * d_offsets (device, n + 1 uint64, 8-byte aligned): where each name starts
+ * and, last, the total, from a device scan of the lengths.  An index that is
+ * not below n_nodes or a span outside the arena counts as an empty name.
+ * *total (host) is the sum of the lengths; where it exceeds cap_names (or
+ * d_names is NULL) the offsets are written and nothing is copied: the caller
+ * comes again with room.  Nothing is unescaped.  Refused before anything is
+ * launched: a null context or total, null arrays with n > 0, a misaligned
+ * d_index or d_offsets.                                                     */
+rcdc_status rcdc_tree_names(rcdc_ctx *ctx, const void *d_text, uint64_t text_len,
+                            const rcdc_trnode *d_nodes, uint64_t n_nodes,
+                            const uint32_t *d_index, uint64_t n, uint64_t *d_offsets,
+                            void *d_names, uint64_t cap_names, uint64_t *total,
+                            void *hip_stream);
+
+/* A level of check_trees judged on the device (commands/check.rs:627-700).
+ * In HBM: the node records of a level (rcdc_tree_nodes, of one call or of
+ * several renumbered into one), d_data_ids with the hit records of a lookup
+ * of them in the data index, d_tree_ids / d_tree_is_dir with the hit records
+ * of a lookup in the tree index (the hits of subtrees of nodes that are no
+ * "dir" and of all-zero ids are there and ignored).
+ *
+ * Findings, in the order check_trees emits them: nodes in order; a "file"
+ * whose content is absent or null gives FILE_HAS_NO_CONTENT; one with content
+ * gives, for each id i in order, FILE_BLOB_HAS_NULL_ID (the id is all zero)
+ * and then FILE_BLOB_NOT_IN_INDEX (hit.count == 0 or hit.loc.pack ==
+ * RCDC_DINDEX_NO_PACK; an all-zero id is looked up like any other), blob_num
+ * = i; a "dir" gives NO_SUBTREE (no subtree), NULL_SUBTREE (an all-zero id)
+ * or SUBTREE_MISSING_IN_INDEX, or nothing; other types give nothing.  One
+ * lane per id and one per node count, two scans place, the same lanes emit: a
+ * finding stands at (id findings before it) + (node findings before it).
+ * *n_findings (host) is their number; where it exceeds cap_findings none is
+ * written and the caller comes again with room.
+ *
+ * Pack marks: d_data_marks[hit.loc.pack] = 1 for every content id of a
+ * "file" that is in the index, d_tree_marks likewise for every dir subtree
+ * that is not all zero and is in the index; n_*_packs are the arrays'
+ * lengths, a pack number past them is not marked.
+ *
+ * Refused before anything is launched: a null context or n_findings, a null
+ * array whose count is not 0, cap_findings > 0 with null d_findings, arrays
+ * not aligned (16 bytes for records and ids, 4 for hits), 2^32 - 1 or more
+ * nodes or ids.                                                              */
+#define RCDC_CKTREE_FILE_HAS_NO_CONTENT       0u
+#define RCDC_CKTREE_FILE_BLOB_HAS_NULL_ID     1u
+#define RCDC_CKTREE_FILE_BLOB_NOT_IN_INDEX    2u
+#define RCDC_CKTREE_NO_SUBTREE                3u
+#define RCDC_CKTREE_NULL_SUBTREE              4u
+#define RCDC_CKTREE_SUBTREE_MISSING_IN_INDEX  5u
+typedef struct {
+    uint32_t node;     /* index of the node record */
+    uint32_t kind;     /* RCDC_CKTREE_*            */
+    uint32_t blob_num; /* the id's place in "content"; 0 for a node finding */
+    uint32_t pad;
+} rcdc_cktree_finding; /* 16 B */
+rcdc_status rcdc_check_trees_level(rcdc_ctx *ctx, const rcdc_trnode *d_nodes, uint64_t n_nodes,
+                                   const void *d_data_ids, const rcdc_dindex_hit *d_data_hits,
+                                   uint64_t n_data_ids, const void *d_tree_ids,
+                                   const uint8_t *d_tree_is_dir,
+                                   const rcdc_dindex_hit *d_tree_hits, uint64_t n_tree_ids,
+                                   uint8_t *d_data_marks, uint64_t n_data_packs,
+                                   uint8_t *d_tree_marks, uint64_t n_tree_packs,
+                                   rcdc_cktree_finding *d_findings, uint64_t cap_findings,
+                                   uint64_t *n_findings, void *hip_stream);
+
 /* ---- pack headers parsed on the device (repofile/packfile.rs) --------------
  * What PackHeader::from_binary (packfile.rs:88-242) reads out of the table at
  * the end of a pack, for a batch of opened (plaintext) headers in HBM:

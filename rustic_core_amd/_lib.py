@@ -48,6 +48,7 @@ EXPORTS = (
     "rcdc_prune_keep",
     "rcdc_index_write", "rcdc_index_write_bound", "rcdc_index_write_span",
     "rcdc_tree_parse", "rcdc_tree_parse_bound", "rcdc_tree_parse_tile",
+    "rcdc_tree_nodes", "rcdc_tree_nodes_bound", "rcdc_tree_names", "rcdc_check_trees_level",
     "rcdc_pack_header_parse", "rcdc_pack_header_parse_bound", "rcdc_pack_header_parse_tile",
     "rcdc_check_packs", "rcdc_check_packs_sort_max",
 )
@@ -381,6 +382,15 @@ def lib() -> ctypes.CDLL:
     L.rcdc_tree_parse_tile.argtypes = []
     L.rcdc_tree_parse.restype = st
     L.rcdc_tree_parse.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, u64, vp, vp, vp]
+    L.rcdc_tree_nodes_bound.restype = None
+    L.rcdc_tree_nodes_bound.argtypes = [u64, P(u64), P(u64), P(u64)]
+    L.rcdc_tree_nodes.restype = st
+    L.rcdc_tree_nodes.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp]
+    L.rcdc_tree_names.restype = st
+    L.rcdc_tree_names.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, P(u64), vp]
+    L.rcdc_check_trees_level.restype = st
+    L.rcdc_check_trees_level.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, vp, u64, vp,
+                                         u64, vp, u64, P(u64), vp]
     L.rcdc_pack_header_parse_bound.restype = u64
     L.rcdc_pack_header_parse_bound.argtypes = [u64]
     L.rcdc_pack_header_parse_tile.restype = u32

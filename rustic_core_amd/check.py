@@ -23,6 +23,7 @@ import calendar
 import ctypes
 import datetime
 import hashlib
+import json
 import random
 import re
 from typing import Callable, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
@@ -634,9 +635,71 @@ def _lookup_level(index, tpe: int, ids: List[bytes], device) -> List[Optional[by
             else packs[int(r[COL_PACK])] for r in h]
 
 
+_NULL_ID = bytes(32)
+# RCDC_CKTREE_*: the kinds of rcdc_check_trees_level, in its numbering
+LEVEL_KINDS = ("FileHasNoContent", "FileBlobHasNullId", "FileBlobNotInIndex", "NoSubTree",
+               "NullSubTree", "SubTreeMissingInIndex")
+# rcdc_cktree_finding as a numpy record
+CKT_FINDING = np.dtype([("node", "<u4"), ("kind", "<u4"), ("blob_num", "<u4"), ("pad", "<u4")])
+NODE_FACTS = ("host", "device")
+
+
+def level_ids(level) -> Tuple[List[bytes], List[bytes]]:
+    """The ids a level looks up: the content ids of file nodes, and the
+    subtrees of dir nodes that are neither absent nor all zero.  ``level``:
+    [(path, [tree.TreeNode])]."""
+    data_ids = [i for _, nodes in level for n in nodes if n.type == "file"
+                for i in n.content or []]
+    tree_ids = [n.subtree for _, nodes in level for n in nodes
+                if n.type == "dir" and n.subtree is not None and n.subtree != _NULL_ID]
+    return data_ids, tree_ids
+
+
+def judge_level(level, data_packs, tree_packs, findings: List[Result], packs: set) -> list:
+    """check_trees' rule for the nodes of a level (check.rs:645-697), which
+    rcdc_check_trees_level is held against.  ``data_packs`` / ``tree_packs``:
+    per id of ``level_ids`` the pack id of its index entry, None for a miss.
+    Appends to ``findings``, adds to ``packs`` and returns [(subtree, path)]
+    of every node with a subtree, in order."""
+    data_packs, tree_packs = iter(data_packs), iter(tree_packs)
+    subtrees = []
+    for path, nodes in level:
+        for n in nodes:
+            where = _join(path, n.name)
+            if n.type == "file":
+                if n.content is None:
+                    findings.append((ERROR, Finding("FileHasNoContent", dict(file=where))))
+                for i, id_ in enumerate(n.content or []):
+                    if id_ == _NULL_ID:
+                        findings.append((ERROR, Finding("FileBlobHasNullId",
+                                                        dict(file=where, blob_num=i))))
+                    pack = next(data_packs)
+                    if pack is None:
+                        findings.append((ERROR, Finding("FileBlobNotInIndex",
+                                                        dict(file=where, blob_id=id_))))
+                    else:
+                        packs.add(pack)
+            elif n.type == "dir":
+                if n.subtree is None:
+                    findings.append((ERROR, Finding("NoSubTree", dict(dir=where))))
+                elif n.subtree == _NULL_ID:
+                    findings.append((ERROR, Finding("NullSubTree", dict(dir=where))))
+                else:
+                    pack = next(tree_packs)
+                    if pack is None:
+                        findings.append((ERROR, Finding("SubTreeMissingInIndex",
+                                                        dict(dir=where, blob_id=n.subtree))))
+                    else:
+                        packs.add(pack)
+            if n.subtree is not None:
+                subtrees.append((n.subtree, where))
+    return subtrees
+
+
 def check_trees(key, index, snap_trees: Sequence[bytes], read_partial: Callable,
                 device: Optional[int] = 0, budget: int = DEFAULT_BUDGET,
-                decode: Optional[Callable] = None, findings: Optional[List[Result]] = None):
+                decode: Optional[Callable] = None, findings: Optional[List[Result]] = None,
+                node_facts: Optional[str] = None, stats: Optional[dict] = None):
     """check_trees (check.rs:627-700) over TreeStreamerOnce.  Returns
     (findings, the set of pack ids the trees refer to).
 
@@ -652,16 +715,33 @@ def check_trees(key, index, snap_trees: Sequence[bytes], read_partial: Callable,
     the level is read -- the findings of earlier levels are in ``findings``
     (pass a list to keep them; ``check_repository`` turns the error into
     ErrorCheckingTrees and an empty pack set).  Then the coalesced pack reads
-    of ``find_used_blobs`` with one ``read.read_blobs`` per group, and the
-    node facts by ``tree.parse_tree_nodes_host``: FileHasNoContent,
-    FileBlobHasNullId, NoSubTree, NullSubTree and the paths.  The level's
-    content ids go to the data index and its dir subtrees to the tree index in
-    one ``lookup`` each: FileBlobNotInIndex, SubTreeMissingInIndex and the
-    packs referred to.  Every subtree of any node is followed once."""
+    of ``find_used_blobs`` with one ``read.read_blobs`` per group.
+
+    ``node_facts`` (with a device; ``device=None`` ignores it) says where the
+    nodes are judged.  "host": every blob's text comes to the host, the node
+    facts by ``tree.parse_tree_nodes_host`` and ``judge_level``, the level's
+    content ids and dir subtrees looked up in one ``lookup`` each.  "device"
+    (None means this): the texts stay in HBM, ``tree.parse_tree_nodes`` gives
+    node records, the id arrays are looked up as they are,
+    rcdc_check_trees_level judges the records and marks the packs, and only
+    the count of findings crosses; names cross for the nodes that have a
+    finding and for the path above them, and a blob outside the device's
+    grammar goes alone through the host rule, at its place.  Both give the
+    same findings in the same order and the same packs.  ``stats`` (a dict)
+    receives ``text_bytes_to_host``, ``name_bytes_to_host`` and
+    ``host_parsed_blobs``; on a clean repository inside the grammar the device
+    route leaves all three 0.  Every subtree of any node is followed once."""
     from .tree import _distinct, parse_tree_nodes_host
+    if node_facts is not None and node_facts not in NODE_FACTS:
+        raise RusticError(ErrorKind.InvalidInput, f"node_facts is one of {NODE_FACTS} or None")
     findings = [] if findings is None else findings
+    stats = {} if stats is None else stats
+    for k in ("text_bytes_to_host", "name_bytes_to_host", "host_parsed_blobs"):
+        stats[k] = 0
+    if device is not None and node_facts != "host":
+        return _check_trees_device(key, index, snap_trees, read_partial, int(device), budget,
+                                   findings, stats)
     packs = set()
-    null = bytes(32)
     frontier = [(t, "") for t in _distinct(snap_trees)]
     visited = {t for t, _ in frontier}
     while frontier:
@@ -670,46 +750,217 @@ def check_trees(key, index, snap_trees: Sequence[bytes], read_partial: Callable,
             texts = _host_texts(key, index, tids, read_partial, decode)
         else:
             texts = _device_texts(key, index, tids, read_partial, int(device), budget)
+            stats["text_bytes_to_host"] += sum(len(t) for t in texts)
+        stats["host_parsed_blobs"] += len(texts)
         level = [(path, parse_tree_nodes_host(text)) for (_, path), text in zip(frontier, texts)]
-        data_ids = [i for _, nodes in level for n in nodes if n.type == "file"
-                    for i in n.content or []]
-        tree_ids = [n.subtree for _, nodes in level for n in nodes
-                    if n.type == "dir" and n.subtree is not None and n.subtree != null]
-        data_packs = iter(_lookup_level(index, DATA, data_ids, device))
-        tree_packs = iter(_lookup_level(index, TREE, tree_ids, device))
+        data_ids, tree_ids = level_ids(level)
+        subtrees = judge_level(level, _lookup_level(index, DATA, data_ids, device),
+                               _lookup_level(index, TREE, tree_ids, device), findings, packs)
         frontier = []
-        for path, nodes in level:
-            for n in nodes:
-                where = _join(path, n.name)
-                if n.type == "file":
-                    if n.content is None:
-                        findings.append((ERROR, Finding("FileHasNoContent", dict(file=where))))
-                    for i, id_ in enumerate(n.content or []):
-                        if id_ == null:
-                            findings.append((ERROR, Finding("FileBlobHasNullId",
-                                                            dict(file=where, blob_num=i))))
-                        pack = next(data_packs)
-                        if pack is None:
-                            findings.append((ERROR, Finding("FileBlobNotInIndex",
-                                                            dict(file=where, blob_id=id_))))
-                        else:
-                            packs.add(pack)
-                elif n.type == "dir":
-                    if n.subtree is None:
-                        findings.append((ERROR, Finding("NoSubTree", dict(dir=where))))
-                    elif n.subtree == null:
-                        findings.append((ERROR, Finding("NullSubTree", dict(dir=where))))
-                    else:
-                        pack = next(tree_packs)
-                        if pack is None:
-                            findings.append((ERROR, Finding("SubTreeMissingInIndex",
-                                                            dict(dir=where, blob_id=n.subtree))))
-                        else:
-                            packs.add(pack)
-                if n.subtree is not None and n.subtree not in visited:
-                    visited.add(n.subtree)
-                    frontier.append((n.subtree, where))
+        for subtree, where in subtrees:
+            if subtree not in visited:
+                visited.add(subtree)
+                frontier.append((subtree, where))
     return findings, packs
+
+
+def run_check_level(res, data_hits, tree_hits, data_marks, tree_marks, device: int = 0,
+                    cap: int = 1024, guard: int = 0):
+    """rcdc_check_trees_level over the outputs of one ``tree.parse_tree_nodes``
+    (``res``; anything with ``node_records``, ``data_ids``, ``tree_ids`` and
+    ``tree_is_dir`` does) and the (n, 6) int32 hit records of its two lookups;
+    the marks are uint8 device tensors, one byte per pack of the type.
+    Returns (count, findings): CKT_FINDING records on the host, None where the
+    count is 0 -- then nothing but the count has crossed.  ``cap``: the room
+    for findings tried first; ``guard``: bytes of 0xA5 kept behind them (the
+    flat tensor is then returned instead), both for tests."""
+    import torch
+    from .crypto import _ctx
+    dev = torch.device("cuda", int(device))
+    al = lambda t: t.clone() if t.numel() and t.data_ptr() % 16 else t
+    nodes, data, tree = al(res.node_records), al(res.data_ids), al(res.tree_ids)
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    count = ctypes.c_uint64(0)
+    with torch.cuda.device(dev):
+        while True:
+            flat = torch.full((cap * 16 + guard,), 0xA5, dtype=torch.uint8, device=dev)
+            _check(_lib.lib().rcdc_check_trees_level(
+                _ctx(int(device)).handle, ptr(nodes), int(nodes.shape[0]), ptr(data),
+                ptr(data_hits), int(data.shape[0]), ptr(tree), ptr(res.tree_is_dir),
+                ptr(tree_hits), int(tree.shape[0]), ptr(data_marks), int(data_marks.numel()),
+                ptr(tree_marks), int(tree_marks.numel()), ptr(flat) if cap else None, cap,
+                ctypes.byref(count), int(torch.cuda.current_stream(dev).cuda_stream)))
+            if int(count.value) <= cap:
+                break
+            cap = int(count.value)  # nothing was written: come again with room
+    n = int(count.value)
+    if guard:
+        return n, flat
+    return n, (flat[:n * 16].cpu().numpy().view(CKT_FINDING) if n else None)
+
+
+class _LevelNames:
+    """The raw names of a level's frontier entries, kept in HBM: per entry
+    the entry of the level before it hangs under and where its name lies (a
+    ``tree.tree_names`` arena of a group, or a path the host already knows).
+    ``path`` builds an entry's path when a finding needs it."""
+
+    def __init__(self, stats):
+        self.levels = [None]  # per level: (parents, part, within, arenas); None: the roots
+        self.known = {}       # (level, entry) -> path
+        self.stats = stats
+
+    def raw(self, arena, i: int) -> str:
+        offsets, names = arena
+        o = offsets[i:i + 2].cpu().numpy()
+        raw = names[int(o[0]):int(o[1])].cpu().numpy().tobytes()
+        self.stats["name_bytes_to_host"] += len(raw)
+        return raw_name(raw)
+
+    def path(self, level: int, j: int) -> str:
+        if self.levels[level] is None:
+            return ""
+        if (level, j) not in self.known:
+            parents, part, within, arenas = self.levels[level]
+            self.known[level, j] = _join(self.path(level - 1, int(parents[j])),
+                                         self.raw(arenas[int(part[j])], int(within[j])))
+        return self.known[level, j]
+
+
+def raw_name(raw: bytes) -> str:
+    """A node's name from the raw bytes between its quotes: the rule
+    ``tree.parse_tree_nodes_host`` applies to the whole blob."""
+    return json.loads(b'"' + bytes(raw) + b'"')
+
+
+def _check_trees_device(key, index, snap_trees, read_partial, device: int, budget: int,
+                        findings: List[Result], stats: dict):
+    """check_trees with the node facts judged in HBM (``check_trees``)."""
+    import torch
+    from .dindex import COL_COUNT, COL_PACK, NO_PACK
+    from .tree import (NODE_SUBTREE, OK, TR_NODE, _blob_text, _distinct, _IdSet, _level_groups,
+                       _Rows, parse_tree_nodes, parse_tree_nodes_host, tree_names)
+    dev = torch.device("cuda", device)
+    packs = set()
+    roots = _distinct(snap_trees)
+    if not roots:
+        return findings, packs
+    names = _LevelNames(stats)
+    with torch.cuda.device(dev):
+        marks = {t: torch.zeros(len(index.packs(t)), dtype=torch.uint8, device=dev)
+                 for t in (DATA, TREE)}
+        empty_hits = torch.empty((0, 6), dtype=torch.int32, device=dev)
+        lookup = lambda t, ids: index.lookup(t, ids) if int(ids.shape[0]) else empty_hits
+        frontier = torch.from_numpy(np.frombuffer(b"".join(roots), np.uint8)
+                                    .reshape(-1, 32).copy()).to(dev)
+        visited = _IdSet(device)
+        try:
+            visited.take(frontier)
+            level = 0
+            while int(frontier.shape[0]):
+                k = int(frontier.shape[0])
+                found = []                 # (frontier position, finding), sorted at the end
+                subtrees = _Rows(k, dev, 32)
+                # per row of subtrees.parts: its blob, its name's arena and place there
+                owner, part, within, arenas = [], [], [], []
+                for js, plain in _level_groups(key, index, frontier, read_partial, device, budget):
+                    res = parse_tree_nodes(plain.data, plain.offsets, plain.lengths, device)
+                    blobs = res.blobs
+                    n, got = run_check_level(res, lookup(DATA, res.data_ids),
+                                             lookup(TREE, res.tree_ids), marks[DATA], marks[TREE],
+                                             device)
+                    if n:
+                        found += _device_findings(names, level, js, plain, res, got, device)
+                    # the names of the nodes with a subtree, in d_tree_ids' order
+                    flags = res.node_records[:, 29]
+                    with_subtree = torch.nonzero(flags & NODE_SUBTREE).reshape(-1)
+                    subtrees.add(js, blobs["tree_start"], blobs["tree_ids"], res.tree_ids)
+                    owner.append(np.repeat(js, blobs["tree_ids"].astype(np.int64)))
+                    part.append(np.full(res.n_tree_ids, len(arenas), np.int64))
+                    within.append(np.arange(res.n_tree_ids, dtype=np.int64))
+                    arenas.append(tree_names(plain.data, res.node_records, with_subtree, device))
+                    # a blob outside the device's grammar: the host rule, at its place
+                    for i in np.nonzero(blobs["status"] != OK)[0]:
+                        text = _blob_text(plain, i)
+                        stats["text_bytes_to_host"] += len(text)
+                        stats["host_parsed_blobs"] += 1
+                        j = int(js[i])
+                        one = [(names.path(level, j), parse_tree_nodes_host(text))]
+                        data_ids, tree_ids = level_ids(one)
+                        mine: List[Result] = []
+                        below = judge_level(one, _lookup_level(index, DATA, data_ids, device),
+                                            _lookup_level(index, TREE, tree_ids, device), mine, packs)
+                        found += [(j, f) for f in mine]
+                        subtrees.add_host(j, b"".join(s for s, _ in below))
+                        owner.append(np.full(len(below), j, np.int64))
+                        part.append(np.full(len(below), len(arenas), np.int64))
+                        within.append(np.arange(len(below), dtype=np.int64))
+                        arenas.append([w for _, w in below])
+                findings += [f for _, f in sorted(found, key=lambda x: x[0])]
+                # the next frontier: the subtrees first reached, in the level's order
+                order = subtrees.order()
+                frontier, new = visited.take_flags(subtrees.gather())
+                rows = order[np.nonzero(new.cpu().numpy())[0]]
+                cat = lambda a: np.concatenate(a) if a else np.zeros(0, np.int64)
+                nxt = (cat(owner)[rows], cat(part)[rows], cat(within)[rows], arenas)
+                names.levels.append(nxt)
+                level += 1
+                # what the host rule reached is a path already
+                for e in np.nonzero([isinstance(arenas[p], list) for p in nxt[1]])[0]:
+                    names.known[level, int(e)] = arenas[int(nxt[1][e])][int(nxt[2][e])]
+        finally:
+            visited.close()
+        for t in (DATA, TREE):
+            ids = index.packs(t)
+            packs |= {ids[int(i)] for i in torch.nonzero(marks[t]).reshape(-1).cpu().numpy()}
+    return findings, packs
+
+
+def _device_findings(names, level: int, js, plain, res, got, device: int) -> list:
+    """The findings of rcdc_check_trees_level (``got``: CKT_FINDING) as
+    check_trees reports them, each with the frontier position of its blob:
+    the records, names and ids of the nodes that have one come to the host."""
+    import torch
+    from .tree import TR_NODE, tree_names
+    dev = res.node_records.device
+    which, inverse = np.unique(got["node"], return_inverse=True)
+    d_which = torch.from_numpy(which.astype(np.int64)).to(dev)
+    recs = res.node_records[d_which].cpu().numpy().reshape(-1).view(TR_NODE)
+    offsets, raw = tree_names(plain.data, res.node_records, d_which, device)
+    offsets, raw = offsets.cpu().numpy(), raw.cpu().numpy().tobytes()
+    names.stats["name_bytes_to_host"] += len(raw)
+    # the ids a finding quotes, one gather per array
+    r_of = recs[inverse]
+    is_data = got["kind"] == LEVEL_KINDS.index("FileBlobNotInIndex")
+    is_tree = got["kind"] == LEVEL_KINDS.index("SubTreeMissingInIndex")
+
+    def rows(t, at):
+        if not len(at):
+            return []
+        got_rows = t[torch.from_numpy(at.astype(np.int64)).to(dev)].cpu().numpy()
+        return [r.tobytes() for r in got_rows]
+    data_rows = iter(rows(res.data_ids, (r_of["data_start"].astype(np.int64) +
+                                         got["blob_num"].astype(np.int64))[is_data]))
+    tree_rows = iter(rows(res.tree_ids, r_of["tree_index"][is_tree]))
+    out = []
+    for f, u in zip(got, inverse):
+        r = recs[u]
+        j = int(js[int(r["blob"])])
+        where = _join(names.path(level, j),
+                      raw_name(raw[int(offsets[u]):int(offsets[u + 1])]))
+        kind = LEVEL_KINDS[int(f["kind"])]
+        if kind == "FileHasNoContent":
+            d = dict(file=where)
+        elif kind == "FileBlobHasNullId":
+            d = dict(file=where, blob_num=int(f["blob_num"]))
+        elif kind == "FileBlobNotInIndex":
+            d = dict(file=where, blob_id=next(data_rows))
+        elif kind == "SubTreeMissingInIndex":
+            d = dict(dir=where, blob_id=next(tree_rows))
+        else:
+            d = dict(dir=where)
+        out.append((j, (ERROR, Finding(kind, d))))
+    return out
 
 
 # ---- check_pack for a batch (check.rs:304-316, 718-814) -------------------------------
@@ -1115,7 +1366,8 @@ def check_repository(key, list_with_size: Callable, read_full: Callable, read_pa
                      snap_trees: Sequence[bytes], read_data: bool = False,
                      read_data_subset: ReadSubset = ReadSubset(), device: Optional[int] = 0,
                      budget: int = DEFAULT_BUDGET, decode: Optional[Callable] = None,
-                     rng: Optional[random.Random] = None) -> CheckResults:
+                     rng: Optional[random.Random] = None, node_facts: Optional[str] = None,
+                     stats: Optional[dict] = None) -> CheckResults:
     """check_repository (check.rs:225-321) without the cache and hot-file
     passes.  ``list_with_size(file_type)`` lists [(id, size)] of "index" or
     "pack" files, ``read_full(file_type, id)`` returns a file's bytes,
@@ -1128,7 +1380,8 @@ def check_repository(key, list_with_size: Callable, read_full: Callable, read_pa
     ``read_data``, the collected packs that are not missing and that the trees
     refer to -- tree packs first, each with its id and blobs only, as the
     reference's ``into_index().into_iter()`` gives them -- through
-    ``read_data_subset.apply`` and ``check_pack_batch``."""
+    ``read_data_subset.apply`` and ``check_pack_batch``.  ``node_facts`` and
+    ``stats`` are ``check_trees``'s."""
     results = CheckResults()
     index_files = [IndexFile.from_json(_decrypt_file(key, read_full("index", bytes(i)), device,
                                                      decode))
@@ -1146,7 +1399,7 @@ def check_repository(key, list_with_size: Callable, read_full: Callable, read_pa
     try:
         try:
             _, used = check_trees(key, index, snap_trees, read_partial, device, budget, decode,
-                                  results)
+                                  results, node_facts, stats)
         except RusticError as e:
             results.append((ERROR, Finding("ErrorCheckingTrees", dict(source=e))))
             used = set()

@@ -1,6 +1,6 @@
-// rcdc_tree_parse (include/rcdc.h): the host half -- argument checks, the
-// tile table, scratch memory and the order of the launches.  The kernels are
-// in rcdc_trparse.hip.
+// rcdc_tree_parse and rcdc_tree_nodes (include/rcdc.h): the host half --
+// argument checks, the tile table, scratch memory and the order of the
+// launches.  The kernels are in rcdc_trparse.hip.
 //
 // The call stops the stream twice: once after the structural pass, to size
 // the record arrays from its four totals, and once at the end, to hand the
@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <string>
 #include <vector>
 
 #include "rcdc_host.h"
@@ -48,26 +49,44 @@ void rcdc_tree_parse_bound(uint64_t len, uint64_t *max_data_ids, uint64_t *max_t
 
 uint32_t rcdc_tree_parse_tile(void) { return RCDC_TRPARSE_TILE; }
 
-rcdc_status rcdc_tree_parse(rcdc_ctx *ctx, const void *d_text, uint64_t text_len,
-                            const rcdc_trparse_ref *refs, uint32_t n_blobs, void *d_data_ids,
-                            uint64_t cap_data_ids, void *d_tree_ids, uint8_t *d_tree_is_dir,
-                            uint64_t cap_tree_ids, rcdc_trparse_blob *blobs,
-                            rcdc_trparse_result *result, void *hip_stream) {
-    if (!ctx) return invalid("rcdc_tree_parse: ctx is NULL");
-    if (!result) return invalid("rcdc_tree_parse: result is NULL");
-    if (n_blobs && (!refs || !blobs)) return invalid("rcdc_tree_parse: null array");
+}  // extern "C"
+
+namespace {
+
+struct Fail {
+    const char *fn;
+    rcdc_status operator()(const char *what) const {
+        return invalid((std::string(fn) + ": " + what).c_str());
+    }
+};
+
+// rcdc_tree_parse, and rcdc_tree_nodes where `nodes` is set: then the grammar
+// is G_N, d_nodes takes the records and node_start (n_blobs) their starts.
+rcdc_status tree_parse(const char *fn, bool nodes, rcdc_ctx *ctx, const void *d_text,
+                       uint64_t text_len, const rcdc_trparse_ref *refs, uint32_t n_blobs,
+                       void *d_data_ids, uint64_t cap_data_ids, void *d_tree_ids,
+                       uint8_t *d_tree_is_dir, uint64_t cap_tree_ids, rcdc_trnode *d_nodes,
+                       uint64_t cap_nodes, uint64_t *node_start, rcdc_trparse_blob *blobs,
+                       rcdc_trparse_result *result, void *hip_stream) {
+    const Fail fail = {fn};
+    if (!ctx) return fail("ctx is NULL");
+    if (!result) return fail("result is NULL");
+    if (n_blobs && (!refs || !blobs)) return fail("null array");
+    if (nodes && n_blobs && !d_nodes) return fail("d_nodes is NULL");
+    uint64_t need_nodes = 0;
     uint64_t need_data = 0, need_tree = 0, n_tiles = 0, bytes = 0;
     std::vector<uint32_t> tile_first(n_blobs + 1u, 0u);
     const uint64_t mis = (uint64_t)(uintptr_t)d_text & 15u;
     for (uint32_t b = 0; b < n_blobs; b++) {
         const rcdc_trparse_ref r = refs[b];
         if (r.off > text_len || r.len > text_len - r.off)
-            return invalid("rcdc_tree_parse: a ref lies outside the arena");
-        if (r.len && !d_text) return invalid("rcdc_tree_parse: d_text is NULL");
-        uint64_t d = 0, t = 0;
-        rcdc_tree_parse_bound(r.len, &d, &t, nullptr);
+            return fail("a ref lies outside the arena");
+        if (r.len && !d_text) return fail("d_text is NULL");
+        uint64_t d = 0, t = 0, nn = 0;
+        rcdc_tree_parse_bound(r.len, &d, &t, &nn);
         need_data += d;
         need_tree += t;
+        need_nodes += nn;
         bytes += r.len;
         tile_first[b] = (uint32_t)n_tiles;
         if (r.len) {
@@ -76,14 +95,16 @@ rcdc_status rcdc_tree_parse(rcdc_ctx *ctx, const void *d_text, uint64_t text_len
         }
         // every count of the structural pass is a count of bytes
         if (n_tiles >= 0xFFFFFFFFull || bytes >= 0xFFFFFFFFull)
-            return invalid("rcdc_tree_parse: the batch holds 2^32 - 1 bytes or more");
+            return fail("the batch holds 2^32 - 1 bytes or more");
     }
     tile_first[n_blobs] = (uint32_t)n_tiles;
     if ((d_data_ids && cap_data_ids < need_data) ||
-        ((d_tree_ids || d_tree_is_dir) && cap_tree_ids < need_tree))
-        return invalid("rcdc_tree_parse: capacities below rcdc_tree_parse_bound");
+        ((d_tree_ids || d_tree_is_dir) && cap_tree_ids < need_tree) ||
+        (nodes && cap_nodes < need_nodes))
+        return fail("capacities below rcdc_tree_parse_bound");
     if (((uintptr_t)d_data_ids & 15u) || ((uintptr_t)d_tree_ids & 15u))
-        return invalid("rcdc_tree_parse: the id arrays must be 16-byte aligned");
+        return fail("the id arrays must be 16-byte aligned");
+    if (nodes && ((uintptr_t)d_nodes & 15u)) return fail("d_nodes must be 16-byte aligned");
     *result = rcdc_trparse_result{};
     if (n_blobs == 0) return RCDC_OK;
 
@@ -95,6 +116,7 @@ rcdc_status rcdc_tree_parse(rcdc_ctx *ctx, const void *d_text, uint64_t text_len
     a.text_len = text_len;
     a.n_blobs = n_blobs;
     a.n_tiles = (uint32_t)n_tiles;
+    a.gn = nodes ? 1u : 0u;
     rcdc_trparse_ref *d_refs = nullptr;
     uint32_t *d_tile_first = nullptr;
     HIP_TRY(sc.get(&d_refs, n_blobs));
@@ -134,19 +156,68 @@ rcdc_status rcdc_tree_parse(rcdc_ctx *ctx, const void *d_text, uint64_t text_len
     // counted, not written: no capacity to hold the lanes to
     a.cap_data_ids = d_data_ids ? cap_data_ids : ~0ull;
     a.cap_tree_ids = (d_tree_ids || d_tree_is_dir) ? cap_tree_ids : ~0ull;
+    if (nodes) {
+        a.nodes = d_nodes;
+        a.cap_nodes = cap_nodes;
+        HIP_TRY(sc.get(&a.node_start, n_blobs));
+    }
     HIP_TRY(launch_tr_parse(a, st));
     uint32_t tot[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(tot, adds + (uint64_t)a.total.nodes * 4, sizeof tot,
                           hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(blobs, a.blobs, n_blobs * sizeof *blobs, hipMemcpyDeviceToHost, st));
+    if (nodes)
+        HIP_TRY(hipMemcpyAsync(node_start, a.node_start, n_blobs * sizeof *node_start,
+                              hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (tot[0] > a.cap_data_ids || tot[1] > a.cap_tree_ids)
-        return set_error(RCDC_ERR_INTERNAL, "rcdc_tree_parse: more output than the bound allows");
+    if (tot[0] > a.cap_data_ids || tot[1] > a.cap_tree_ids || (nodes && tot[2] > cap_nodes))
+        return set_error(RCDC_ERR_INTERNAL,
+                         (std::string(fn) + ": more output than the bound allows").c_str());
     result->data_ids = tot[0];
     result->tree_ids = tot[1];
     result->nodes = tot[2];
     for (uint32_t b = 0; b < n_blobs; b++)
         result->blobs_not_parsed += blobs[b].status != RCDC_TRPARSE_OK;
+    return RCDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+rcdc_status rcdc_tree_parse(rcdc_ctx *ctx, const void *d_text, uint64_t text_len,
+                            const rcdc_trparse_ref *refs, uint32_t n_blobs, void *d_data_ids,
+                            uint64_t cap_data_ids, void *d_tree_ids, uint8_t *d_tree_is_dir,
+                            uint64_t cap_tree_ids, rcdc_trparse_blob *blobs,
+                            rcdc_trparse_result *result, void *hip_stream) {
+    return tree_parse("rcdc_tree_parse", false, ctx, d_text, text_len, refs, n_blobs, d_data_ids,
+                      cap_data_ids, d_tree_ids, d_tree_is_dir, cap_tree_ids, nullptr, 0, nullptr,
+                      blobs, result, hip_stream);
+}
+
+void rcdc_tree_nodes_bound(uint64_t len, uint64_t *max_data_ids, uint64_t *max_tree_ids,
+                           uint64_t *max_nodes) {
+    rcdc_tree_parse_bound(len, max_data_ids, max_tree_ids, max_nodes);
+}
+
+rcdc_status rcdc_tree_nodes(rcdc_ctx *ctx, const void *d_text, uint64_t text_len,
+                            const rcdc_trparse_ref *refs, uint32_t n_blobs, void *d_data_ids,
+                            uint64_t cap_data_ids, void *d_tree_ids, uint8_t *d_tree_is_dir,
+                            uint64_t cap_tree_ids, rcdc_trnode *d_nodes, uint64_t cap_nodes,
+                            rcdc_trnodes_blob *blobs, rcdc_trparse_result *result,
+                            void *hip_stream) {
+    if (n_blobs && !blobs) return invalid("rcdc_tree_nodes: null array");
+    std::vector<rcdc_trparse_blob> ids(n_blobs);
+    std::vector<uint64_t> starts(n_blobs, 0);
+    const rcdc_status st =
+        tree_parse("rcdc_tree_nodes", true, ctx, d_text, text_len, refs, n_blobs, d_data_ids,
+                   cap_data_ids, d_tree_ids, d_tree_is_dir, cap_tree_ids, d_nodes, cap_nodes,
+                   starts.data(), ids.data(), result, hip_stream);
+    if (st != RCDC_OK) return st;
+    for (uint32_t b = 0; b < n_blobs; b++)
+        blobs[b] = rcdc_trnodes_blob{ids[b].status,     ids[b].nodes,      ids[b].data_ids,
+                                     ids[b].tree_ids,   ids[b].data_start, ids[b].tree_start,
+                                     starts[b]};
     return RCDC_OK;
 }
 

@@ -47,11 +47,17 @@ struct TrClose {
     uint32_t blob, rank;  // id opens (c4) / node opens (c2) before it
 };
 constexpr uint32_t kTrNodeOk = 1u, kTrNodeFile = 2u, kTrNodeDir = 4u, kTrNodeSubtree = 8u;
+// for the node records of rcdc_tree_nodes: "content" is an array, the raw
+// name holds a backslash, and the type as its index in NODE_TYPES
+constexpr uint32_t kTrNodeContent = 16u, kTrNodeNameEsc = 32u, kTrNodeTypeShift = 8u;
 struct TrNodeTmp {
     uint32_t subtree[8];
     uint32_t flags;     // kTrNode*
     uint32_t blob;
     uint32_t id0, nids; // its content: id opens [id0, id0 + nids)
+    uint64_t name_pos;  // the first byte after the name's opening quote
+    uint32_t name_len;  // raw bytes up to its closing quote
+    uint32_t pad;
 };
 
 struct TrArgs {
@@ -60,6 +66,7 @@ struct TrArgs {
     const rcdc_trparse_ref *refs;   // device copy
     const uint32_t *tile_first;     // n_blobs + 1
     uint32_t n_blobs, n_tiles;
+    uint32_t gn;                    // the grammar is G_N (rcdc_tree_nodes): a dir may lack its subtree
     // scratch
     TrTileSum *sums;
     TrTileIn *ins;
@@ -79,6 +86,11 @@ struct TrArgs {
     uint8_t *data_ids, *tree_ids, *tree_is_dir;
     uint64_t cap_data_ids, cap_tree_ids;
     rcdc_trparse_blob *blobs;
+    // rcdc_tree_nodes only (null otherwise): the node records, and per blob
+    // where its records start
+    rcdc_trnode *nodes;
+    uint64_t cap_nodes;
+    uint64_t *node_start;
 };
 
 // the structural pass up to the totals in counts[n_tiles]

@@ -2,6 +2,8 @@
 // find_used_blobs and TreeStreamerOnce read out of them (commands/prune.rs:
 // 1582-1632, blob/tree.rs:618-800).  gfx950, wave64.  The plan is
 // rcdc_ixparse.hip's; what is new is that strings hold backslashes.
+// rcdc_tree_nodes is the same kernels with TrArgs::gn set (the grammar G_N)
+// and one more at the end, which writes a record per node.
 //
 // The structural pass.  A byte is ESCAPED when an odd run of backslashes ends
 // right before it; an escaped byte and a backslash that is not escaped count
@@ -333,30 +335,34 @@ __device__ __forceinline__ bool utf8_tail(Cur &c, int n, int lo, int hi) {
     return true;
 }
 
-// a string of G_T
-__device__ bool parse_string(Cur &c) {
-    if (!c.eat('"')) return false;
+// a string of G_T: 0 where it is none, else kStrOk, with kStrEsc where it
+// holds a backslash
+constexpr uint32_t kStrOk = 1u, kStrEsc = 2u;
+__device__ uint32_t parse_string(Cur &c) {
+    if (!c.eat('"')) return 0u;
+    uint32_t found = kStrOk;
     for (;;) {
         const int ch = c.peek();
-        if (ch < 0x20) return false;  // a control byte, or the end of the blob
+        if (ch < 0x20) return 0u;  // a control byte, or the end of the blob
         c.pos++;
-        if (ch == '"') return true;
+        if (ch == '"') return found;
         if (ch == '\\') {
+            found |= kStrEsc;
             const int e = c.peek();
             c.pos++;
             if (e == 'u') {
-                if (c.end - c.pos < 4 || c.pos > c.end) return false;
+                if (c.end - c.pos < 4 || c.pos > c.end) return 0u;
                 int v = 0;
                 for (int i = 0; i < 4; i++) {
                     const int h = hexval(c.j[c.pos + i]);
-                    if (h < 0) return false;
+                    if (h < 0) return 0u;
                     v = v * 16 + h;
                 }
-                if (v >= 0xD800 && v <= 0xDFFF) return false;
+                if (v >= 0xD800 && v <= 0xDFFF) return 0u;
                 c.pos += 4;
             } else if (e != '"' && e != '\\' && e != '/' && e != 'b' && e != 'f' && e != 'n' &&
                        e != 'r' && e != 't') {
-                return false;
+                return 0u;
             }
         } else if (ch >= 0x80) {
             bool ok;
@@ -368,7 +374,7 @@ __device__ bool parse_string(Cur &c) {
             else if (ch >= 0xF1 && ch <= 0xF3) ok = utf8_tail(c, 3, 0x80, 0xBF);
             else if (ch == 0xF4) ok = utf8_tail(c, 3, 0x80, 0x8F);
             else ok = false;
-            if (!ok) return false;
+            if (!ok) return 0u;
         }
     }
 }
@@ -489,16 +495,27 @@ __device__ bool parse_node(const TrArgs &a, Cur &c, const TrNodeOpen &r, TrNodeT
         c.ws();
         bool ok;
         switch (k) {
-        case K_NAME: case K_LINKTARGET:
-            ok = parse_string(c);
+        case K_NAME: case K_LINKTARGET: {
+            const uint64_t quote = c.pos;
+            const uint32_t str = parse_string(c);
+            ok = str != 0u;
+            if (ok && k == K_NAME) {
+                o->name_pos = quote + 1;
+                o->name_len = (uint32_t)(c.pos - quote - 2);
+                if (str & kStrEsc) o->flags |= kTrNodeNameEsc;
+            }
             break;
-        case K_TYPE:
+        }
+        case K_TYPE:  // the index in NODE_TYPES
             ok = true;
             if (c.lit("\"file\"", 6)) type = kTrNodeFile;
-            else if (c.lit("\"dir\"", 5)) type = kTrNodeDir;
-            else if (c.lit("\"symlink\"", 9)) symlink = true;
-            else ok = c.lit("\"dev\"", 5) || c.lit("\"chardev\"", 9) || c.lit("\"fifo\"", 6) ||
-                      c.lit("\"socket\"", 8);
+            else if (c.lit("\"dir\"", 5)) type = kTrNodeDir | (1u << kTrNodeTypeShift);
+            else if (c.lit("\"symlink\"", 9)) symlink = true, type = 2u << kTrNodeTypeShift;
+            else if (c.lit("\"dev\"", 5)) type = 3u << kTrNodeTypeShift;
+            else if (c.lit("\"chardev\"", 9)) type = 4u << kTrNodeTypeShift;
+            else if (c.lit("\"fifo\"", 6)) type = 5u << kTrNodeTypeShift;
+            else if (c.lit("\"socket\"", 8)) type = 6u << kTrNodeTypeShift;
+            else ok = false;
             break;
         case K_MODE: case K_UID: case K_GID:
             ok = c.lit("null", 4) || parse_uint(c, 0xFFFFFFFFull);
@@ -516,6 +533,7 @@ __device__ bool parse_node(const TrArgs &a, Cur &c, const TrNodeOpen &r, TrNodeT
                 ok = skip_array(c, '"', a.c4, c4++, a.total.c4, r.blob, &rank) && rank >= r.id_rank;
                 o->id0 = r.id_rank;
                 o->nids = ok ? rank - r.id_rank : 0u;
+                o->flags |= kTrNodeContent;
             }
             break;
         case K_SUBTREE:
@@ -545,7 +563,8 @@ __device__ bool parse_node(const TrArgs &a, Cur &c, const TrNodeOpen &r, TrNodeT
     o->flags |= type;
     if ((seen & 3u) != 3u) return false;
     if (symlink && !((seen >> K_LINKTARGET) & 1u)) return false;
-    if (type == kTrNodeDir && !(o->flags & kTrNodeSubtree)) return false;
+    // G_T leaves a dir without a subtree to the host; G_N records it
+    if ((type & kTrNodeDir) && !(o->flags & kTrNodeSubtree) && !a.gn) return false;
     return after_element(c, '{');
 }
 
@@ -830,6 +849,26 @@ __global__ __launch_bounds__(256) void rcdc_tr_blob_kernel(TrArgs a) {
     r.data_start = x0.x;
     r.tree_start = x0.y;
     a.blobs[b] = r;
+    if (a.node_start) a.node_start[b] = x0.z;
+}
+
+// rcdc_tree_nodes: one lane per node writes its record; the record's index is
+// the count of nodes of OK blobs before it, which the numbering scanned
+__global__ __launch_bounds__(256) void rcdc_tr_record_kernel(TrArgs a) {
+    const uint32_t i = blockIdx.x * kTrBlock + threadIdx.x;
+    if (i >= a.total.nodes) return;
+    const TrNodeTmp *p = a.tmp_nodes + i;
+    if (!(p->flags & kTrNodeOk) || !a.blob_ok[p->blob]) return;
+    const u32x4v x = reinterpret_cast<const u32x4v *>(a.adds)[i];
+    if (x.z >= a.cap_nodes) return;  // the bound: never
+    uint32_t flags = 0;
+    if (p->flags & kTrNodeContent) flags |= RCDC_TRNODE_CONTENT;
+    if (p->flags & kTrNodeSubtree) flags |= RCDC_TRNODE_SUBTREE;
+    if (p->flags & kTrNodeNameEsc) flags |= RCDC_TRNODE_NAME_ESC;
+    const uint32_t type = (p->flags >> kTrNodeTypeShift) & 7u;
+    u32x4v *d = reinterpret_cast<u32x4v *>(a.nodes + x.z);
+    d[0] = u32x4v{(uint32_t)p->name_pos, (uint32_t)(p->name_pos >> 32), p->name_len, p->blob};
+    d[1] = u32x4v{x.x, (p->flags & kTrNodeContent) ? p->nids : 0u, x.y, type | (flags << 8)};
 }
 
 __global__ __launch_bounds__(256) void rcdc_tr_subtree_kernel(TrArgs a) {
@@ -907,6 +946,8 @@ hipError_t launch_tr_parse(const TrArgs &a, hipStream_t st) {
         TR_LAUNCH(rcdc_tr_subtree_kernel, tr_blocks(a.total.nodes, kTrBlock), kTrBlock, a);
     if (a.total.ids && a.data_ids)
         TR_LAUNCH(rcdc_tr_scatter_kernel, tr_blocks(a.total.ids, kTrBlock), kTrBlock, a);
+    if (a.total.nodes && a.nodes)
+        TR_LAUNCH(rcdc_tr_record_kernel, tr_blocks(a.total.nodes, kTrBlock), kTrBlock, a);
     return hipSuccess;
 }
 

@@ -16,6 +16,10 @@ reads the ids out of their text, and two id-only ``rcdc_dindex`` sets keep
 lookup hits the pack reads need; the result is a device tensor, which is what
 ``PrunePlan.from_entries(used_ids=...)`` takes.  A blob outside the device's
 grammar goes through ``parse_tree_host``.
+
+``parse_tree_nodes`` (rcdc_tree_nodes) is the same parse with a record per
+node, and ``tree_names`` (rcdc_tree_names) gathers raw names by node index:
+what ``check.check_trees`` judges a level from without the text leaving HBM.
 """
 from __future__ import annotations
 
@@ -34,6 +38,12 @@ OK, NOT_PARSED = 0, 1  # RCDC_TRPARSE_OK / RCDC_TRPARSE_NOT_PARSED
 TR_REF = np.dtype([("off", "<u8"), ("len", "<u8")])
 TR_BLOB = np.dtype([("status", "<u4"), ("nodes", "<u4"), ("data_ids", "<u4"), ("tree_ids", "<u4"),
                     ("data_start", "<u8"), ("tree_start", "<u8")])
+# rcdc_trnode / rcdc_trnodes_blob (rcdc_tree_nodes)
+TR_NODE = np.dtype([("name_off", "<u8"), ("name_len", "<u4"), ("blob", "<u4"),
+                    ("data_start", "<u4"), ("n_content", "<u4"), ("tree_index", "<u4"),
+                    ("type", "u1"), ("flags", "u1"), ("pad", "<u2")])
+TR_NODES_BLOB = np.dtype(TR_BLOB.descr + [("node_start", "<u8")])
+NODE_CONTENT, NODE_SUBTREE, NODE_NAME_ESC = 1, 2, 4  # RCDC_TRNODE_*
 DESERIALIZE_MESSAGE = "Failed to deserialize tree from JSON."  # blob/tree.rs:156
 NODE_TYPES = ("file", "dir", "symlink", "dev", "chardev", "fifo", "socket")
 DEFAULT_BUDGET = 1 << 30
@@ -66,13 +76,21 @@ class ParsedTrees:
     (m, 32) uint8 and ``tree_is_dir`` (m,) uint8 device tensors (None where
     not asked for), cut to the rows that were written; the counts
     ``n_data_ids``, ``n_tree_ids`` and ``nodes`` (also where the ids were only
-    counted); ``blobs`` (TR_BLOB) on the host."""
+    counted); ``blobs`` (TR_BLOB) on the host.  From rcdc_tree_nodes
+    (``parse_tree_nodes``) also ``node_records``, a (nodes, 32) uint8 device
+    tensor of TR_NODE records, and ``blobs`` is TR_NODES_BLOB."""
 
-    def __init__(self, data_ids, tree_ids, tree_is_dir, blobs, n_data_ids, n_tree_ids, nodes, raw):
+    def __init__(self, data_ids, tree_ids, tree_is_dir, blobs, n_data_ids, n_tree_ids, nodes, raw,
+                 node_records=None):
         self.data_ids, self.tree_ids, self.tree_is_dir = data_ids, tree_ids, tree_is_dir
         self.blobs, self.nodes = blobs, nodes
         self.n_data_ids, self.n_tree_ids = n_data_ids, n_tree_ids
         self.raw = raw  # the flat allocations behind the arrays, guard bytes included
+        self.node_records = node_records
+
+    def nodes_host(self) -> np.ndarray:
+        """The node records as a TR_NODE array on the host."""
+        return self.node_records.cpu().numpy().reshape(-1).view(TR_NODE)
 
 
 def parse_trees(d_text, offs, lens, device: int = 0, want=(True, True), guard: int = 0,
@@ -82,6 +100,19 @@ def parse_trees(d_text, offs, lens, device: int = 0, want=(True, True), guard: i
     subtree ids); what is not wanted is counted only.  ``guard``: that many
     bytes of 0xA5 behind every output array (in ``raw``), and ``caps``: the
     (content, subtree) capacities instead of the bound's, both for tests."""
+    return _parse(d_text, offs, lens, device, want, guard, caps, False)
+
+
+def parse_tree_nodes(d_text, offs, lens, device: int = 0, want=(True, True), guard: int = 0,
+                     caps=None) -> ParsedTrees:
+    """``parse_trees`` by rcdc_tree_nodes: the grammar is G_N (a dir node may
+    lack its subtree), the id arrays are the same, and ``node_records`` holds
+    one TR_NODE per node of every OK blob.  ``caps``: (content, subtree, node)
+    capacities."""
+    return _parse(d_text, offs, lens, device, want, guard, caps, True)
+
+
+def _parse(d_text, offs, lens, device, want, guard, caps, with_nodes: bool) -> ParsedTrees:
     import torch
     from .crypto import _ctx
     dev = torch.device("cuda", int(device))
@@ -97,9 +128,11 @@ def parse_trees(d_text, offs, lens, device: int = 0, want=(True, True), guard: i
     ln = refs["len"].astype(np.uint64)
     cap_d = int(((ln + np.uint64(1)) // np.uint64(67)).sum())
     cap_t = int(((ln + np.uint64(1)) // np.uint64(102)).sum())
+    cap_n = int(((ln + np.uint64(1)) // np.uint64(25)).sum())
     if caps is not None:
         cap_d, cap_t = int(caps[0]), int(caps[1])
-    blobs = np.zeros(n, TR_BLOB)
+        cap_n = int(caps[2]) if len(caps) > 2 else cap_n
+    blobs = np.zeros(n, TR_NODES_BLOB if with_nodes else TR_BLOB)
     result = _lib.TrparseResult()
     raw = []
 
@@ -113,15 +146,50 @@ def parse_trees(d_text, offs, lens, device: int = 0, want=(True, True), guard: i
         tree = alloc(cap_t * 32).view(cap_t, 32) if want[1] else None
         is_dir = alloc(cap_t) if want[1] else None
         ptr = lambda a: None if a is None else a.data_ptr()
-        _check(_lib.lib().rcdc_tree_parse(
-            _ctx(int(device)).handle, d_text.data_ptr() if d_text.numel() else None,
-            int(d_text.numel()), refs.ctypes.data, n, ptr(data), cap_d, ptr(tree), ptr(is_dir),
-            cap_t, blobs.ctypes.data, ctypes.byref(result),
-            int(torch.cuda.current_stream(dev).cuda_stream)))
-    nd, nt = int(result.data_ids), int(result.tree_ids)
+        head = (_ctx(int(device)).handle, d_text.data_ptr() if d_text.numel() else None,
+                int(d_text.numel()), refs.ctypes.data, n, ptr(data), cap_d, ptr(tree), ptr(is_dir),
+                cap_t)
+        tail = (blobs.ctypes.data, ctypes.byref(result),
+                int(torch.cuda.current_stream(dev).cuda_stream))
+        if with_nodes:
+            records = alloc(cap_n * 32).view(cap_n, 32)
+            _check(_lib.lib().rcdc_tree_nodes(*head, records.data_ptr(), cap_n, *tail))
+        else:
+            records = None
+            _check(_lib.lib().rcdc_tree_parse(*head, *tail))
+    nd, nt, nn = int(result.data_ids), int(result.tree_ids), int(result.nodes)
     return ParsedTrees(None if data is None else data[:nd], None if tree is None else tree[:nt],
-                       None if is_dir is None else is_dir[:nt], blobs, nd, nt, int(result.nodes),
-                       raw)
+                       None if is_dir is None else is_dir[:nt], blobs, nd, nt, nn, raw,
+                       None if records is None else records[:nn])
+
+
+def tree_names(d_text, node_records, d_index, device: int = 0, guard: int = 0):
+    """rcdc_tree_names: the raw names of the nodes ``d_index`` (an int32 or
+    uint32 device tensor of indices into ``node_records``) out of the arena
+    ``d_text``, back to back.  Returns (offsets, names): an int64 device
+    tensor of len(d_index) + 1 entries and a uint8 device tensor.  ``guard``:
+    that many bytes of 0xA5 behind the names, for tests."""
+    import torch
+    from .crypto import _ctx
+    dev = torch.device("cuda", int(device))
+    n = int(d_index.shape[0])
+    with torch.cuda.device(dev):
+        d_index = d_index.to(torch.int32).contiguous()
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        total = ctypes.c_uint64(0)
+        cap = 32 * n + 256
+        while True:
+            flat = torch.full((cap + guard,), 0xA5, dtype=torch.uint8, device=dev)
+            _check(_lib.lib().rcdc_tree_names(
+                _ctx(int(device)).handle, d_text.data_ptr() if d_text.numel() else None,
+                int(d_text.numel()), node_records.data_ptr() if node_records.numel() else None,
+                int(node_records.shape[0]), d_index.data_ptr() if n else None, n,
+                offsets.data_ptr(), flat.data_ptr(), cap, ctypes.byref(total),
+                int(torch.cuda.current_stream(dev).cuda_stream)))
+            if int(total.value) <= cap:
+                break
+            cap = int(total.value)  # the offsets are written: come again with room
+    return offsets, (flat if guard else flat[:int(total.value)])
 
 
 # ---- the host rule ------------------------------------------------------------
@@ -341,10 +409,15 @@ class _IdSet:
     def take(self, ids, select=None):
         """``ids``: (n, 32) uint8 device tensor; ``select``: n flags (uint8)
         or None for all.  Returns the new rows in order, now in the set."""
+        return self.take_flags(ids, select)[0]
+
+    def take_flags(self, ids, select=None):
+        """``take``, and with the rows their flags: n uint8, 1 where the row
+        is one of those returned."""
         torch = self._torch
         n = int(ids.shape[0])
         if not n:
-            return ids[:0]
+            return ids[:0], torch.empty(0, dtype=torch.uint8, device=self._dev)
         ids = ids.contiguous()
         if ids.data_ptr() % 16:
             ids = ids.clone()
@@ -359,7 +432,7 @@ class _IdSet:
             if int(fresh.shape[0]):
                 _check(_lib.lib().rcdc_dindex_add(self._h, fresh.data_ptr(), None,
                                                   int(fresh.shape[0]), 1, s))  # DEVICE_PTRS
-        return fresh
+        return fresh, new
 
 
 def _level_reads(index, frontier_host: np.ndarray, hits: np.ndarray):
@@ -415,74 +488,98 @@ def _load_group(group, read_partial, dev):
     return raw, parts
 
 
-def _gather(parts: list, starts: np.ndarray, counts: np.ndarray, dev, width: int):
-    """Rows [starts[j], starts[j] + counts[j]) of the concatenation of
-    ``parts`` for j in order, as one tensor."""
-    import torch
-    shape = (0, width) if width else (0,)
-    allrows = torch.cat(parts) if parts else torch.empty(shape, dtype=torch.uint8, device=dev)
+def _order(starts: np.ndarray, counts: np.ndarray) -> np.ndarray:
+    """The rows [starts[j], starts[j] + counts[j]) for j in order, as indices."""
     total = int(counts.sum())
-    if not total:
-        return allrows[:0]
     first = np.cumsum(counts) - counts
-    idx = np.repeat(starts - first, counts) + np.arange(total, dtype=np.int64)
-    if total == int(allrows.shape[0]) and np.array_equal(idx, np.arange(total)):
-        return allrows
-    return allrows[torch.from_numpy(idx).to(dev)]
+    return np.repeat(starts - first, counts) + np.arange(total, dtype=np.int64)
+
+
+class _Rows:
+    """Rows of a level that arrive group by group -- a group's blobs are a
+    subset of the frontier in the order of the pack reads -- and are put back
+    into the frontier's order: blob j's rows are [at[j], at[j] + n[j]) of the
+    parts' concatenation."""
+
+    def __init__(self, k: int, dev, width: int):
+        self.at, self.n = np.zeros(k, np.int64), np.zeros(k, np.int64)
+        self.parts, self.base, self.dev, self.width = [], 0, dev, width
+
+    def add(self, js, starts, counts, rows) -> None:
+        self.at[js] = self.base + np.asarray(starts, np.int64)
+        self.n[js] = counts
+        self.parts.append(rows)
+        self.base += int(rows.shape[0])
+
+    def add_host(self, j: int, data: bytes) -> None:
+        """``data`` (host bytes) as the rows of blob j."""
+        import torch
+        rows = np.frombuffer(data, np.uint8).reshape((-1, self.width) if self.width else (-1,))
+        self.add([j], [0], [len(rows)], torch.from_numpy(rows.copy()).to(self.dev))
+
+    def order(self) -> np.ndarray:
+        return _order(self.at, self.n)
+
+    def gather(self):
+        import torch
+        shape = (0, self.width) if self.width else (0,)
+        allrows = torch.cat(self.parts) if self.parts \
+            else torch.empty(shape, dtype=torch.uint8, device=self.dev)
+        idx = self.order()
+        if not len(idx):
+            return allrows[:0]
+        if len(idx) == int(allrows.shape[0]) and np.array_equal(idx, np.arange(len(idx))):
+            return allrows
+        return allrows[torch.from_numpy(idx).to(self.dev)]
+
+
+def _level_groups(key, index, frontier, read_partial, device: int, budget: int):
+    """What a level of ``find_used_blobs`` and of ``check.check_trees`` share:
+    one lookup of the frontier ((k, 32) device tensor; an id the index lacks
+    raises before anything is read), the coalesced pack reads in groups of at
+    most ``budget`` decoded bytes and one ``read.read_blobs`` per group.
+    Yields (js, plain) per group: the frontier positions of its blobs and
+    their decoded texts in HBM."""
+    from .dindex import TREE
+    from .index import IndexBlob
+    from .read import read_blobs
+    from .restore import _groups
+    hits = index.lookup(TREE, frontier).cpu().numpy().view(np.uint32)
+    reads = _level_reads(index, frontier.cpu().numpy(), hits)
+    for group in _groups(reads, int(budget)):
+        raw, parts = _load_group(group, read_partial, frontier.device)
+        owners = sorted((dests[0], o + bl.offset - r.offset, bl)
+                        for r, o in parts for bl, dests in r.blobs)
+        entries = [IndexBlob(b"", TREE, at, bl.length, bl.uncompressed_length or None)
+                   for _, at, bl in owners]
+        yield np.array([j for j, _, _ in owners], np.int64), read_blobs(key, raw, entries, device)
+
+
+def _blob_text(plain, i: int) -> bytes:
+    """Blob i of a ``read_blobs`` result on the host."""
+    o, ln = int(plain.offsets[i]), int(plain.lengths[i])
+    return plain.data[o:o + ln].cpu().numpy().tobytes()
 
 
 def _device_level(key, index, frontier, read_partial, device: int, budget: int):
     """One level on the device: (data ids, tree ids, is_dir) of the trees in
     ``frontier`` ((k, 32) device tensor), in the order blob, node, array."""
-    import torch
-    from .dindex import TREE
-    from .index import IndexBlob
-    from .read import read_blobs
-    from .restore import _groups
     dev = frontier.device
     k = int(frontier.shape[0])
-    hits = index.lookup(TREE, frontier).cpu().numpy().view(np.uint32)
-    reads = _level_reads(index, frontier.cpu().numpy(), hits)
-    # per frontier blob: where its ids are in the concatenated outputs
-    d_at, d_n = np.zeros(k, np.int64), np.zeros(k, np.int64)
-    t_at, t_n = np.zeros(k, np.int64), np.zeros(k, np.int64)
-    d_parts, t_parts, f_parts = [], [], []
-    d_base = t_base = 0
-
-    def append(data, tree, flags):
-        nonlocal d_base, t_base
-        d_parts.append(data)
-        t_parts.append(tree)
-        f_parts.append(flags)
-        d_base += int(data.shape[0])
-        t_base += int(tree.shape[0])
-
-    for group in _groups(reads, int(budget)):
-        raw, parts = _load_group(group, read_partial, dev)
-        owners = sorted((dests[0], o + bl.offset - r.offset, bl)
-                        for r, o in parts for bl, dests in r.blobs)
-        entries = [IndexBlob(b"", TREE, at, bl.length, bl.uncompressed_length or None)
-                   for _, at, bl in owners]
-        plain = read_blobs(key, raw, entries, device)
+    data, tree, flags = _Rows(k, dev, 32), _Rows(k, dev, 32), _Rows(k, dev, 0)
+    for js, plain in _level_groups(key, index, frontier, read_partial, device, budget):
         res = parse_trees(plain.data, plain.offsets, plain.lengths, device)
-        js = np.array([j for j, _, _ in owners], np.int64)
-        d_at[js] = d_base + res.blobs["data_start"].astype(np.int64)
-        d_n[js] = res.blobs["data_ids"]
-        t_at[js] = t_base + res.blobs["tree_start"].astype(np.int64)
-        t_n[js] = res.blobs["tree_ids"]
-        append(res.data_ids, res.tree_ids, res.tree_is_dir)
+        data.add(js, res.blobs["data_start"], res.blobs["data_ids"], res.data_ids)
+        tree.add(js, res.blobs["tree_start"], res.blobs["tree_ids"], res.tree_ids)
+        flags.add(js, res.blobs["tree_start"], res.blobs["tree_ids"], res.tree_is_dir)
         # the host rule for the blobs the device left: their ids join the level's arrays
         for i in np.nonzero(res.blobs["status"] != OK)[0]:
-            o, ln = int(plain.offsets[i]), int(plain.lengths[i])
-            _, data, tree = parse_tree_host(plain.data[o:o + ln].cpu().numpy().tobytes())
+            _, d, t = parse_tree_host(_blob_text(plain, i))
             j = int(js[i])
-            d_at[j], d_n[j], t_at[j], t_n[j] = d_base, len(data), t_base, len(tree)
-            up = lambda b, w: torch.from_numpy(
-                np.frombuffer(b, np.uint8).reshape((-1, w) if w else (-1,)).copy()).to(dev)
-            append(up(b"".join(data), 32), up(b"".join(i for i, _ in tree), 32),
-                   up(bytes(int(f) for _, f in tree), 0))
-    return (_gather(d_parts, d_at, d_n, dev, 32), _gather(t_parts, t_at, t_n, dev, 32),
-            _gather(f_parts, t_at, t_n, dev, 0))
+            data.add_host(j, b"".join(d))
+            tree.add_host(j, b"".join(i for i, _ in t))
+            flags.add_host(j, bytes(int(f) for _, f in t))
+    return data.gather(), tree.gather(), flags.gather()
 
 
 def _host_blob(key, index, tree_id: bytes, read_partial, decode, device) -> bytes:

@@ -1,0 +1,286 @@
+"""check_trees with the node facts judged on the device: rcdc_check_trees_level
+alone against the rule over records (tests/tree_nodes_model.py), and
+check.check_trees with ``node_facts="device"`` against ``node_facts="host"``
+and ``device=None`` on built repositories and the reference's recorded ones."""
+import types
+
+import numpy as np
+import pytest
+
+from oracle import oracle, zstd_ref as zr
+from tests import tree_nodes_model as model
+from tests import used_blobs_repo as ubr
+from tests.check_cases import REPOS, Repo, normal, recorded
+from tests.check_trees_repo import MISSING, NULL, Packed, build
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 64
+F, D = 0, 1  # node types
+
+
+def _id(n: int) -> bytes:
+    return bytes([n % 251 + 1]) * 32
+
+
+class _Level:
+    """Synthetic node records, ids and hits of a level, built node by node."""
+
+    def __init__(self):
+        self.nodes, self.data_ids, self.data_hits = [], [], []
+        self.tree_ids, self.tree_hits, self.is_dir = [], [], []
+
+    def node(self, tpe, content=None, subtree=None):
+        """content: None or [(id, pack or None)]; subtree: None or (id, pack or None)."""
+        flags = (model.CONTENT if content is not None else 0) | (model.SUBTREE if subtree else 0)
+        self.nodes.append((0, 0, 0, len(self.data_ids), len(content or []), len(self.tree_ids), tpe,
+                           flags, 0))
+        hit = lambda p: (0, 0) if p is None else (1, p)
+        if tpe == F:
+            for i, p in content or []:
+                self.data_ids.append(i)
+                self.data_hits.append(hit(p))
+        if subtree:
+            self.tree_ids.append(subtree[0])
+            self.tree_hits.append(hit(subtree[1]))
+            self.is_dir.append(int(tpe == D))
+
+    def run(self, n_packs=(40, 40), cap=1024):
+        import torch
+        from rustic_core_amd.check import run_check_level
+        up = lambda a: torch.from_numpy(a).to("cuda:0")
+        ids = lambda x: up(np.frombuffer(b"".join(x), np.uint8).reshape(-1, 32).copy())
+        hits = lambda x: up(np.array([(0 if c else -1, c, p if c else -1, 0, 0, 0) for c, p in x],
+                                     np.int64).astype(np.int32).reshape(-1, 6))
+        res = types.SimpleNamespace(
+            node_records=up(model.node_array(self.nodes).view(np.uint8).reshape(-1, 32).copy()),
+            data_ids=ids(self.data_ids), tree_ids=ids(self.tree_ids),
+            tree_is_dir=up(np.array(self.is_dir, np.uint8)))
+        marks = [torch.zeros(n, dtype=torch.uint8, device="cuda:0") for n in n_packs]
+        want, dp, tp = model.level_rule(self.nodes, self.data_ids, self.data_hits, self.tree_ids,
+                                        self.tree_hits)
+        n, got = run_check_level(res, hits(self.data_hits), hits(self.tree_hits), marks[0], marks[1],
+                                 cap=cap)
+        assert n == len(want)
+        assert (got is None) == (n == 0)
+        if n:
+            assert [(int(f["node"]), int(f["kind"]), int(f["blob_num"])) for f in got] == want
+            assert not got["pad"].any()
+        for m, packs, size in zip(marks, (dp, tp), n_packs):
+            assert set(np.nonzero(m.cpu().numpy())[0].tolist()) == {p for p in packs if p < size}
+        # the guard bytes behind exactly n findings
+        n2, flat = run_check_level(res, hits(self.data_hits), hits(self.tree_hits), marks[0], marks[1],
+                                   cap=max(n, 1), guard=GUARD)
+        assert n2 == n and (flat[n * 16:].cpu().numpy() == 0xA5).all()
+        assert int(flat.numel()) == max(n, 1) * 16 + GUARD
+        return want, dp, tp
+
+
+def test_level_each_kind_and_the_order(gpu_ctx):
+    lv = _Level()
+    lv.node(F)                                             # FileHasNoContent
+    lv.node(F, [])                                         # nothing
+    lv.node(F, [(_id(1), 3), (NULL, None), (_id(2), None), (NULL, None)])
+    lv.node(D)                                             # NoSubTree
+    lv.node(D, None, (NULL, None))                         # NullSubTree
+    lv.node(D, None, (NULL, 5))                            # NullSubTree: its hit is ignored
+    lv.node(D, None, (_id(3), None))                       # SubTreeMissingInIndex
+    lv.node(D, None, (_id(4), 7))                          # fine: pack 7 of the tree packs
+    lv.node(2, [(_id(5), None)], (_id(6), None))           # a symlink: nothing of it is judged
+    lv.node(F, [(_id(7), 9)], (_id(8), None))              # a file's subtree is not judged
+    lv.node(D, [(_id(9), None)], (_id(4), 0xFFFFFFFF))     # count 1, NO_PACK: missing
+    lv.node(F, [(_id(1), 0xFFFFFFFF)])                     # the same for a content id
+    want, dp, tp = lv.run()
+    assert [(k, model.KINDS[kind], n) for k, kind, n in want] == [
+        (0, "FileHasNoContent", 0), (2, "FileBlobHasNullId", 1), (2, "FileBlobNotInIndex", 1),
+        (2, "FileBlobNotInIndex", 2), (2, "FileBlobHasNullId", 3), (2, "FileBlobNotInIndex", 3),
+        (3, "NoSubTree", 0), (4, "NullSubTree", 0), (5, "NullSubTree", 0),
+        (6, "SubTreeMissingInIndex", 0), (10, "SubTreeMissingInIndex", 0),
+        (11, "FileBlobNotInIndex", 0)]
+    assert (dp, tp) == ({3, 9}, {7})
+    # a pack number past the marks is not marked
+    lv.run(n_packs=(4, 4))
+    # an all-zero id the index does hold: a null id, and a hit
+    one = _Level()
+    one.node(F, [(NULL, 2)])
+    assert one.run()[0] == [(0, 1, 0)]
+
+
+def test_level_of_no_nodes_and_clean_levels(gpu_ctx):
+    assert _Level().run() == ([], set(), set())
+    lv = _Level()
+    for k in range(300):
+        lv.node(F, [(_id(k + j), (k + j) % 40) for j in range(k % 5)])
+        lv.node(D, None, (_id(k), k % 40))
+    want, dp, tp = lv.run()
+    assert want == [] and len(dp) == 40 and len(tp) == 40
+
+
+def test_level_a_file_of_4097_ids(gpu_ctx):
+    """One lane per id: findings at ids 0, 63, 64 and 4096 of one file,
+    between nodes with findings of their own."""
+    lv = _Level()
+    lv.node(D)
+    content = [(_id(i), i % 30) for i in range(4097)]
+    content[0] = (_id(0), None)
+    content[63] = (NULL, None)
+    content[64] = (NULL, 3)
+    content[4096] = (_id(4096), None)
+    lv.node(F, content)
+    lv.node(F)
+    want, _, _ = lv.run()
+    assert want == [(0, 3, 0), (1, 2, 0), (1, 1, 63), (1, 2, 63), (1, 1, 64), (1, 2, 4096), (2, 0, 0)]
+
+
+@pytest.mark.parametrize("n", (1025, 2049))
+def test_level_findings_across_the_scan_blocks(gpu_ctx, n):
+    """n findings from nodes and ids in turns: the scans cross their blocks
+    of 1024 and the first call's room (1024 findings) is too small."""
+    lv = _Level()
+    k = count = 0
+    while count + 5 <= n:
+        lv.node(F, [(_id(k), k % 9), (NULL, None), (_id(k + 1), None)])   # 3 findings
+        lv.node(D if k % 2 else F)                                      # 1
+        lv.node(D, None, (_id(k), None if k % 3 else 4))                # 1, or none
+        lv.node(2)
+        count += 5 if k % 3 else 4
+        k += 1
+    for _ in range(n - count):
+        lv.node(F)
+    want, _, _ = lv.run()
+    assert len(want) == n
+    lv.run(cap=n)  # room for exactly n
+
+
+# ---- check_trees ------------------------------------------------------------------------
+
+_PACKED = {}
+
+
+def _packed(gpu_ctx, which):
+    if which not in _PACKED:  # built once for the module, never changed
+        _PACKED[which] = Packed(gpu_ctx, build() if which == "findings" else ubr.build())
+    return _PACKED[which]
+
+
+def _three(p, snapshots, without=()):
+    """check_trees by the three routes: [(findings, packs or the error's text, stats)]."""
+    from rustic_core_amd.check import check_trees
+    from rustic_core_amd.errors import RusticError
+    out = []
+    dx = p.index(without)
+    for device, facts, index in ((0, "device", dx), (0, "host", dx), (None, None, p.host_index(without))):
+        findings, stats = [], {}
+        try:
+            _, packs = check_trees(p.key, index, snapshots, p.reader(), device=device,
+                                   findings=findings, node_facts=facts, stats=stats)
+        except RusticError as e:
+            packs = str(e)
+        out.append((findings, packs, stats))
+    dx.close()
+    return out
+
+
+def _kinds(findings):
+    return [(f.kind, dict(f.fields).get("file", dict(f.fields).get("dir"))) for _, f in findings]
+
+
+def test_findings_repository(gpu_ctx):
+    """Every kind but SubTreeMissingInIndex (which ends the walk one level
+    later: the next test), the path three levels down, the tree reached
+    twice, the tree of the host rule and the one below it."""
+    p = _packed(gpu_ctx, "findings")
+    dev, host, py = _three(p, p.repo.snapshots)
+    assert dev[0] == host[0] == py[0]
+    assert isinstance(dev[1], set) and dev[1] == host[1] == py[1]
+    got = _kinds(dev[0])
+    assert set(k for k, _ in got) == set(model.KINDS) - {"SubTreeMissingInIndex"}
+    for want in (("FileHasNoContent", "kinds/none"), ("FileHasNoContent", "kinds/nullcontent"),
+                 ("FileBlobHasNullId", "kinds/four"), ("FileBlobNotInIndex", "kinds/four"),
+                 ("NoSubTree", "kinds/nosub"), ("NoSubTree", "kinds/nosub2"),
+                 ("NullSubTree", "kinds/nullsub"), ("FileHasNoContent", '/abs/q"uote/dA/lost'),
+                 ("FileHasNoContent", "twice_a/s"), ("FileHasNoContent", "host/hf"),
+                 ("FileBlobNotInIndex", "host/below/hb")):
+        assert want in got, want
+    assert not any(w.startswith("twice_b") for _, w in got)
+    four = [(f.kind, dict(f.fields).get("blob_num"), dict(f.fields).get("blob_id"))
+            for _, f in dev[0] if dict(f.fields).get("file") == "kinds/four"]
+    assert four == [("FileBlobHasNullId", 1, None), ("FileBlobNotInIndex", None, NULL),
+                    ("FileBlobNotInIndex", None, ubr.did(MISSING[0])),
+                    ("FileBlobHasNullId", 3, None), ("FileBlobNotInIndex", None, NULL)]
+    # every data pack (each blob a pack holds is some file's), and tree packs
+    assert {ip.id for ip in p.data_packs} < dev[1] <= {ip.id for ip in p.tree_packs + p.data_packs}
+    assert dev[2]["host_parsed_blobs"] == 2            # mid7 and host
+    assert dev[2]["text_bytes_to_host"] == sum(len(p.repo.trees[p.names[t]]) for t in ("mid7", "host"))
+    assert 0 < dev[2]["name_bytes_to_host"] < 400
+    assert host[2]["host_parsed_blobs"] > 40 and host[2]["name_bytes_to_host"] == 0
+    assert host[2]["text_bytes_to_host"] > 10 * dev[2]["text_bytes_to_host"]
+    # one group per blob: the same
+    from rustic_core_amd.check import check_trees
+    dx = p.index()
+    small = check_trees(p.key, dx, p.repo.snapshots, p.reader(), budget=1, node_facts="device")
+    dx.close()
+    assert small[0] == dev[0] and small[1] == dev[1]
+
+
+def test_a_subtree_the_index_lacks(gpu_ctx):
+    """SubTreeMissingInIndex, and with it all six kinds in one list: the
+    walk then fails at the next level as the reference's does, with the same
+    error by every route and the findings up to there kept."""
+    p = _packed(gpu_ctx, "findings")
+    dev, host, py = _three(p, p.repo.snapshots[3:], without=(p.names["gone-leaf"],))
+    assert dev[0] == host[0] == py[0]
+    assert isinstance(dev[1], str) and dev[1] == host[1] == py[1]
+    assert f"Tree ID `{p.names['gone-leaf'].hex()}` not found in index" in dev[1]
+    assert set(k for k, _ in _kinds(dev[0])) == set(model.KINDS)
+    assert ("SubTreeMissingInIndex", "kinds/gone") in _kinds(dev[0])
+
+
+def test_a_clean_repository_stays_on_the_device(gpu_ctx, monkeypatch):
+    """The point of the device route: with every tree inside the grammar and
+    nothing to report, no text, no name and no parsed blob reaches the host --
+    the host parser is not even callable here."""
+    from rustic_core_amd import tree
+    from rustic_core_amd.check import check_trees
+
+    def never(text):
+        raise AssertionError("a tree blob's text reached the host parser")
+    p = _packed(gpu_ctx, "clean")
+    roots = [p.repo.snapshots[0], p.repo.snapshots[2]]  # root1 alone reaches mid7
+    assert p.names["mid7"] not in [t for lv in ubr.walk(p.repo, roots)[1] for t in lv]
+    py = check_trees(p.key, p.host_index(), roots, p.reader(), device=None)
+    dx = p.index()
+    monkeypatch.setattr(tree, "parse_tree_nodes_host", never)
+    stats = {}
+    got = check_trees(p.key, dx, roots, p.reader(), node_facts="device", stats=stats)
+    assert got == py and got[0] == [] and len(got[1]) > 3
+    assert stats == {"text_bytes_to_host": 0, "name_bytes_to_host": 0, "host_parsed_blobs": 0}
+    with pytest.raises(AssertionError):
+        check_trees(p.key, dx, roots, p.reader(), node_facts="host")
+    monkeypatch.undo()
+    # with the tree outside the grammar back in: that one blob alone
+    stats = {}
+    got = check_trees(p.key, dx, p.repo.snapshots, p.reader(), node_facts="device", stats=stats)
+    dx.close()
+    assert got == check_trees(p.key, p.host_index(), p.repo.snapshots, p.reader(), device=None)
+    assert stats["host_parsed_blobs"] == 1
+    assert stats["text_bytes_to_host"] == len(p.repo.trees[p.names["mid7"]])
+
+
+@pytest.mark.parametrize("name", REPOS)
+def test_recorded_repositories(gpu_ctx, name):
+    """tests/test_gpu_check.py's expectations by the device route, and the
+    blobs it left to the host: as many as the model puts outside G_N."""
+    from rustic_core_amd.check import check_repository
+    from rustic_core_amd.crypto import Key
+    from rustic_core_amd.tree import snapshot_trees
+    repo = Repo(name, oracle)
+    k = Key(repo.master)
+    trees = snapshot_trees(k, repo.snapshots(), device=0, decode=zr.decompress)
+    stats = {}
+    got = check_repository(k, repo.list_with_size, repo.read_full, repo.read_partial, trees,
+                           read_data=True, device=0, decode=zr.decompress, node_facts="device",
+                           stats=stats)
+    assert normal(got) == recorded(name)
+    assert stats["host_parsed_blobs"] == model.OUTSIDE_GN[name]
+    assert stats["text_bytes_to_host"] == 0
