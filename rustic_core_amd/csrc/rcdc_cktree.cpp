@@ -15,25 +15,6 @@
 
 using namespace rcdc;
 
-namespace {
-
-// device allocations of one call
-struct Scratch {
-    std::vector<void *> ptrs;
-    ~Scratch() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    hipError_t get(uint64_t **out, uint64_t n) {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, (n ? n : 1) * sizeof(uint64_t));
-        if (e == hipSuccess) ptrs.push_back(p);
-        *out = static_cast<uint64_t *>(p);
-        return e;
-    }
-};
-
-}  // namespace
-
 extern "C" {
 
 rcdc_status rcdc_tree_names(rcdc_ctx *ctx, const void *d_text, uint64_t text_len,

@@ -18,31 +18,19 @@
 // workgroup over their sums, and the sums added back.
 
 #include "rcdc_cktree.h"
+#include "rcdc_wave.h"
 
 namespace {
 
 using namespace rcdc;
 
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-
-__device__ __forceinline__ u64 wave_incl_add(u64 v) {
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const u64 o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
 
 // One workgroup of kCtScan: the sum of the values of the threads before this
 // one, and *all: of all of them.
 __device__ u64 block_excl(u64 x, u64 *lds /* 16 */, u64 *all) {
     const uint32_t lane = lane_id(), wave = threadIdx.x / 64;
-    const u64 inc = wave_incl_add(x);
+    const u64 inc = wave_incl_add64(x);
     __syncthreads();  // a call before this one has read lds
     if (lane == 63) lds[wave] = inc;
     __syncthreads();
@@ -217,41 +205,33 @@ __global__ __launch_bounds__(256) void rcdc_ct_name_copy_kernel(CtNamesArgs a) {
 
 namespace rcdc {
 
-static inline uint32_t ct_blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
-#define CT_LAUNCH(kernel, grid, block, ...)                                        \
-    do {                                                                           \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);   \
-        if (hipError_t e_ = hipGetLastError(); e_ != hipSuccess) return e_;        \
-    } while (0)
-
 hipError_t launch_ct_scan(uint64_t *v, uint64_t n, uint64_t *sums, hipStream_t st) {
     const uint64_t m = (n + kCtScan - 1) / kCtScan;
-    if (m) CT_LAUNCH(rcdc_ct_scan_kernel, (uint32_t)m, kCtScan, v, n, sums);
-    CT_LAUNCH(rcdc_ct_scan_sums_kernel, 1, kCtScan, sums, m);
-    CT_LAUNCH(rcdc_ct_scan_apply_kernel, m ? (uint32_t)m : 1u, kCtScan, v, n, sums, m);
+    if (m) RCDC_LAUNCH(rcdc_ct_scan_kernel, (uint32_t)m, kCtScan, v, n, sums);
+    RCDC_LAUNCH(rcdc_ct_scan_sums_kernel, 1, kCtScan, sums, m);
+    RCDC_LAUNCH(rcdc_ct_scan_apply_kernel, m ? (uint32_t)m : 1u, kCtScan, v, n, sums, m);
     return hipSuccess;
 }
 
 hipError_t launch_ct_count(const CtLevelArgs &a, hipStream_t st) {
-    if (a.n_data) CT_LAUNCH(rcdc_ct_id_count_kernel, ct_blocks(a.n_data, kCtBlock), kCtBlock, a);
-    if (a.n_nodes) CT_LAUNCH(rcdc_ct_node_count_kernel, ct_blocks(a.n_nodes, kCtBlock), kCtBlock, a);
+    if (a.n_data) RCDC_LAUNCH(rcdc_ct_id_count_kernel, blocks(a.n_data, kCtBlock), kCtBlock, a);
+    if (a.n_nodes) RCDC_LAUNCH(rcdc_ct_node_count_kernel, blocks(a.n_nodes, kCtBlock), kCtBlock, a);
     return hipSuccess;
 }
 
 hipError_t launch_ct_emit(const CtLevelArgs &a, hipStream_t st) {
-    if (a.n_data) CT_LAUNCH(rcdc_ct_id_emit_kernel, ct_blocks(a.n_data, kCtBlock), kCtBlock, a);
-    if (a.n_nodes) CT_LAUNCH(rcdc_ct_node_emit_kernel, ct_blocks(a.n_nodes, kCtBlock), kCtBlock, a);
+    if (a.n_data) RCDC_LAUNCH(rcdc_ct_id_emit_kernel, blocks(a.n_data, kCtBlock), kCtBlock, a);
+    if (a.n_nodes) RCDC_LAUNCH(rcdc_ct_node_emit_kernel, blocks(a.n_nodes, kCtBlock), kCtBlock, a);
     return hipSuccess;
 }
 
 hipError_t launch_ct_name_lens(const CtNamesArgs &a, hipStream_t st) {
-    if (a.n) CT_LAUNCH(rcdc_ct_name_len_kernel, ct_blocks(a.n, kCtBlock), kCtBlock, a);
+    if (a.n) RCDC_LAUNCH(rcdc_ct_name_len_kernel, blocks(a.n, kCtBlock), kCtBlock, a);
     return hipSuccess;
 }
 
 hipError_t launch_ct_name_copy(const CtNamesArgs &a, hipStream_t st) {
-    if (a.n) CT_LAUNCH(rcdc_ct_name_copy_kernel, ct_blocks(a.n, kCtBlock / 64), kCtBlock, a);
+    if (a.n) RCDC_LAUNCH(rcdc_ct_name_copy_kernel, blocks(a.n, kCtBlock / 64), kCtBlock, a);
     return hipSuccess;
 }
 

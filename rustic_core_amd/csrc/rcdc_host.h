@@ -1,7 +1,8 @@
 // rcdc_host.h -- what the host halves of the library share: the entry points
 // rcdc_runtime.cpp exports to the other units, the device guard, the error
-// helpers and the owning buffers (DevBuf, PinnedBuf).  Host code only (rcdc_host_sha.cpp is
-// built without HIP and does not include it).
+// helpers, the owning buffers (DevBuf, PinnedBuf), and the parsers' per-call
+// Scratch and tile table.  Host code only (rcdc_host_sha.cpp is built without
+// HIP and does not include it).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "../../include/rcdc.h"
 
@@ -59,6 +61,55 @@ inline rcdc_status hip_fail(const char *what, hipError_t e) {
     } while (0)
 
 inline rcdc_status invalid(const char *msg) { return set_error(RCDC_ERR_INVALID_INPUT, msg); }
+
+// The device allocations of one call, freed when it returns.
+struct Scratch {
+    std::vector<void *> ptrs;
+    ~Scratch() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+    template <class T>
+    hipError_t get(T **out, uint64_t n) {
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, (n ? n : 1) * sizeof(T));
+        if (e == hipSuccess) ptrs.push_back(p);
+        *out = static_cast<T *>(p);
+        return e;
+    }
+};
+
+// The tile table of the parsers: the texts refs[0, n) ({off, len}) of the
+// arena at d_arena are cut into tiles of tile_bytes that count from the
+// 16-byte boundary at or before a text's first byte; tile_first[r] is the
+// first tile of ref r and tile_first[n] = n_tiles.  within(len), called once
+// per ref in order, adds what else the caller counts and returns whether that
+// is still below its limit.  Returns the first check that failed; the message
+// is the caller's.
+// TooMany: 2^32 - 1 tiles or more, or within() said that its own count is at
+// the caller's limit; the callers give one message for both.
+enum class TileTable { Ok, RefOutside, ArenaNull, TooMany };
+template <class Ref, class Within>
+TileTable tile_table(const Ref *refs, uint32_t n, uint64_t arena_len, const void *d_arena,
+                     uint32_t tile_bytes, std::vector<uint32_t> &tile_first, uint64_t &n_tiles,
+                     Within within) {
+    tile_first.assign(n + 1ull, 0u);
+    n_tiles = 0;
+    const uint64_t mis = (uint64_t)(uintptr_t)d_arena & 15u;
+    for (uint32_t i = 0; i < n; i++) {
+        const Ref r = refs[i];
+        if (r.off > arena_len || r.len > arena_len - r.off) return TileTable::RefOutside;
+        if (r.len && !d_arena) return TileTable::ArenaNull;
+        const bool ok = within(r.len);
+        tile_first[i] = (uint32_t)n_tiles;
+        if (r.len) {
+            const uint64_t v0 = (r.off + mis) & ~15ull;
+            n_tiles += (r.off + mis + r.len - v0 + tile_bytes - 1) / tile_bytes;
+        }
+        if (n_tiles >= 0xFFFFFFFFull || !ok) return TileTable::TooMany;
+    }
+    tile_first[n] = (uint32_t)n_tiles;
+    return TileTable::Ok;
+}
 
 // A device array that only grows, owned by the object that holds it.  Freed
 // by release() or the destructor: the owner makes its device current and

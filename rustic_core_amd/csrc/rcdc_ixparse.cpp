@@ -16,26 +16,6 @@
 
 using namespace rcdc;
 
-namespace {
-
-// device allocations of one call
-struct Scratch {
-    std::vector<void *> ptrs;
-    ~Scratch() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t get(T **out, uint64_t n) {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, (n ? n : 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(p);
-        *out = static_cast<T *>(p);
-        return e;
-    }
-};
-
-}  // namespace
-
 extern "C" {
 
 void rcdc_index_parse_bound(uint64_t len, uint64_t *max_entries, uint64_t *max_packs) {
@@ -57,26 +37,21 @@ rcdc_status rcdc_index_parse(rcdc_ctx *ctx, const void *d_json, uint64_t json_le
     if (n_files && (!refs || !files || !pack_base || !d_ids || !d_locs))
         return invalid("rcdc_index_parse: null array");
     uint64_t need_entries = 0, need_packs = 0, n_tiles = 0;
-    std::vector<uint32_t> tile_first(n_files + 1u, 0u);
-    const uint64_t mis = (uint64_t)(uintptr_t)d_json & 15u;
-    for (uint32_t f = 0; f < n_files; f++) {
-        const rcdc_ixparse_ref r = refs[f];
-        if (r.off > json_len || r.len > json_len - r.off)
-            return invalid("rcdc_index_parse: a ref lies outside the arena");
-        if (r.len && !d_json) return invalid("rcdc_index_parse: d_json is NULL");
+    std::vector<uint32_t> tile_first;
+    switch (tile_table(refs, n_files, json_len, d_json, kIxTile, tile_first, n_tiles,
+                       [&](uint64_t len) {
         uint64_t e = 0, p = 0;
-        rcdc_index_parse_bound(r.len, &e, &p);
+        rcdc_index_parse_bound(len, &e, &p);
         need_entries += e;
         need_packs += p;
-        tile_first[f] = (uint32_t)n_tiles;
-        if (r.len) {
-            const uint64_t v0 = (r.off + mis) & ~15ull;
-            n_tiles += (r.off + mis + r.len - v0 + kIxTile - 1) / kIxTile;
-        }
-        if (n_tiles >= 0xFFFFFFFFull || need_entries >= 0xFFFFFFFFull)
-            return invalid("rcdc_index_parse: the batch may hold 2^32 - 1 entries or more");
+        return need_entries < 0xFFFFFFFFull;
+    })) {
+    case TileTable::RefOutside: return invalid("rcdc_index_parse: a ref lies outside the arena");
+    case TileTable::ArenaNull: return invalid("rcdc_index_parse: d_json is NULL");
+    case TileTable::TooMany:
+        return invalid("rcdc_index_parse: the batch may hold 2^32 - 1 entries or more");
+    case TileTable::Ok: break;
     }
-    tile_first[n_files] = (uint32_t)n_tiles;
     if (cap_entries < need_entries || cap_packs < need_packs)
         return invalid("rcdc_index_parse: capacities below rcdc_index_parse_bound");
     if (need_packs && !packs) return invalid("rcdc_index_parse: packs is NULL");
@@ -110,17 +85,17 @@ rcdc_status rcdc_index_parse(rcdc_ctx *ctx, const void *d_json, uint64_t json_le
     HIP_TRY(hipMemcpyAsync(&a.total, a.counts + n_tiles, sizeof a.total, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
 
-    HIP_TRY(sc.get(&a.blob_open, a.total.blobs));
-    HIP_TRY(sc.get(&a.pack_open, a.total.packs));
-    HIP_TRY(sc.get(&a.c4, a.total.c4));
-    HIP_TRY(sc.get(&a.c2, a.total.c2));
-    HIP_TRY(sc.get(&a.tmp_ids, (uint64_t)a.total.blobs * 32));
-    HIP_TRY(sc.get(&a.tmp_blobs, a.total.blobs));
-    HIP_TRY(sc.get(&a.tmp_packs, a.total.packs));
+    HIP_TRY(sc.get(&a.blob_open, a.total.n[kIxBlob]));
+    HIP_TRY(sc.get(&a.pack_open, a.total.n[kIxPack]));
+    HIP_TRY(sc.get(&a.c4, a.total.n[kIxC4]));
+    HIP_TRY(sc.get(&a.c2, a.total.n[kIxC2]));
+    HIP_TRY(sc.get(&a.tmp_ids, (uint64_t)a.total.n[kIxBlob] * 32));
+    HIP_TRY(sc.get(&a.tmp_blobs, a.total.n[kIxBlob]));
+    HIP_TRY(sc.get(&a.tmp_packs, a.total.n[kIxPack]));
     HIP_TRY(sc.get(&a.tmp_files, n_files));
     HIP_TRY(sc.get(&a.file_bad, n_files));
     uint32_t *adds = nullptr;
-    HIP_TRY(sc.get(&adds, ((uint64_t)a.total.packs + 1) * 4));
+    HIP_TRY(sc.get(&adds, ((uint64_t)a.total.n[kIxPack] + 1) * 4));
     a.adds = adds;
     HIP_TRY(sc.get(&a.files, n_files));
     HIP_TRY(sc.get(&a.packs, cap_packs));

@@ -5,44 +5,32 @@
 #include <stdint.h>
 
 #include "../../include/rcdc.h"
+#include "rcdc_json_tiles.h"
 
 namespace rcdc {
 
-constexpr uint32_t kIxTile = RCDC_IXPARSE_TILE;  // bytes per tile: one wave, kIxRows rows
-constexpr uint32_t kIxRow = 64 * 16;             // one 16-byte load per lane
-constexpr uint32_t kIxRows = kIxTile / kIxRow;
+constexpr uint32_t kIxTile = RCDC_IXPARSE_TILE;  // bytes per tile: one wave
 constexpr uint32_t kIxBlock = 256;               // 4 tiles per workgroup
 
-// A tile as a function of the state at its first byte: the parity of its
-// quotes, and the change of depth when it starts outside (d0) or inside (d1)
-// a string.
-struct IxTileSum {
-    int32_t d0, d1;
-    uint32_t q;
+// The structural pass's records (rcdc_json_tiles.h).  The event kinds, in
+// the order of TileCounts::n: blob-object opens ('{' at depth 4), pack-object
+// opens ('{' at depth 2), ']' at depth 4 (closes a "blobs" array) and ']' at
+// depth 2 (closes an array of the root).
+enum IxEvent : uint32_t { kIxBlob, kIxPack, kIxC4, kIxC2 };
+struct IxGrammar {
+    // ch is a byte that counts, outside a string; -1: no event
+    RCDC_JT_FN static int event_of(uint8_t ch, int32_t depth) {
+        if (ch == '{') return depth == 4 ? (int)kIxBlob : depth == 2 ? (int)kIxPack : -1;
+        if (ch == ']') return depth == 4 ? (int)kIxC4 : depth == 2 ? (int)kIxC2 : -1;
+        return -1;
+    }
 };
-// The state at a tile's first byte.
-struct IxTileIn {
-    uint32_t instr;
-    int32_t depth;
-};
-// Per tile, then (after the scan) before the tile: blob-object opens ('{' at
-// depth 4), pack-object opens ('{' at depth 2), ']' at depth 4 (closes a
-// "blobs" array) and ']' at depth 2 (closes an array of the root).
-struct IxCounts {
-    uint32_t blobs, packs, c4, c2;
-};
-struct IxBlobOpen {
-    uint64_t pos;
-    uint32_t file, pad;
-};
-struct IxPackOpen {
-    uint64_t pos;
-    uint32_t file, blob_rank, c4_rank, pad;
-};
-struct IxClose {
-    uint64_t pos;
-    uint32_t file, rank;  // blob opens (c4) / pack opens (c2) before it
-};
+using IxTileSum = jt::TileSum;
+using IxTileIn = jt::TileIn;
+using IxCounts = jt::TileCounts;
+using IxBlobOpen = jt::TileOpen;        // ref: the file
+using IxPackOpen = jt::TileOpenRanked;  // rank_a: blob opens, rank_b: ']' at depth 4 before it
+using IxClose = jt::TileClose;          // rank: blob opens (c4) / pack opens (c2) before it
 struct IxBlobTmp {
     uint32_t offset, length, ulen, type;
 };

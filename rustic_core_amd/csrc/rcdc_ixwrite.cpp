@@ -23,11 +23,11 @@ namespace {
 
 // The device memory of one call: one allocation, carved up.  (One
 // allocation because hipFree waits for the device each time.)
-struct Scratch {
+struct CarvedScratch {
     uint8_t *base = nullptr;
     uint64_t used = 0;
     std::vector<std::pair<void **, uint64_t>> parts;
-    ~Scratch() {
+    ~CarvedScratch() {
         if (base) (void)hipFree(base);
     }
     template <class T>
@@ -153,7 +153,7 @@ rcdc_status rcdc_index_write(rcdc_ctx *ctx, const void *d_ids, uint64_t id_strid
 
     DeviceGuard g(ctx_device(ctx));
     hipStream_t st = (hipStream_t)hip_stream;
-    Scratch sc;
+    CarvedScratch sc;
     IxwArgs a = {};
     a.ids = static_cast<const uint8_t *>(d_ids);
     a.off = static_cast<const uint8_t *>(d_offset);

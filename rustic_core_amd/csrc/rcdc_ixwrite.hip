@@ -30,12 +30,11 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "rcdc_ixwrite.h"
+#include "rcdc_wave.h"
 
 namespace {
 
 using namespace rcdc;
-
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
 struct Widen {
     __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
@@ -101,23 +100,6 @@ __global__ __launch_bounds__(kIxwBlock) void ixw_packs(IxwArgs a) {
                  (a.epos[a.wfirst[p + 1]] - a.epos[a.wfirst[p]]) + pack_tail_len(pk);
 }
 
-__device__ __forceinline__ uint64_t wave_incl_add64(uint64_t v) {
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)v, d, 64);
-        const uint32_t hi = __shfl_up((uint32_t)(v >> 32), d, 64);
-        if (lane >= d) v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_bcast64(uint64_t v, uint32_t src) {
-    const uint32_t lo = __shfl((uint32_t)v, src, 64);
-    const uint32_t hi = __shfl((uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 // one wave: the files' lengths and their 16-byte aligned offsets
 __global__ __launch_bounds__(64) void ixw_files(IxwArgs a) {
     const uint32_t lane = threadIdx.x;
@@ -137,7 +119,7 @@ __global__ __launch_bounds__(64) void ixw_files(IxwArgs a) {
             a.fout[f].len = len;
             if (f == a.n_files - 1) *a.total = off + len;
         }
-        carry += wave_bcast64(incl, 63);
+        carry += shfl64(incl, 63);
     }
 }
 

@@ -15,26 +15,6 @@
 
 using namespace rcdc;
 
-namespace {
-
-// device allocations of one call
-struct Scratch {
-    std::vector<void *> ptrs;
-    ~Scratch() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t get(T **out, uint64_t n) {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, (n ? n : 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(p);
-        *out = static_cast<T *>(p);
-        return e;
-    }
-};
-
-}  // namespace
-
 extern "C" {
 
 uint64_t rcdc_pack_header_parse_bound(uint64_t len) { return len / 37u; }
@@ -52,23 +32,19 @@ rcdc_status rcdc_pack_header_parse(rcdc_ctx *ctx, const void *d_plain, uint64_t 
     if (n_headers && (!refs || !headers || !pack_base || !d_ids || !d_locs))
         return invalid("rcdc_pack_header_parse: null array");
     uint64_t need_entries = 0, n_tiles = 0;
-    std::vector<uint32_t> tile_first(n_headers + 1ull, 0u);
-    const uint64_t mis = (uint64_t)(uintptr_t)d_plain & 15u;
-    for (uint32_t h = 0; h < n_headers; h++) {
-        const rcdc_pkhdr_ref r = refs[h];
-        if (r.off > plain_len || r.len > plain_len - r.off)
-            return invalid("rcdc_pack_header_parse: a ref lies outside the arena");
-        if (r.len && !d_plain) return invalid("rcdc_pack_header_parse: d_plain is NULL");
-        need_entries += rcdc_pack_header_parse_bound(r.len);
-        tile_first[h] = (uint32_t)n_tiles;
-        if (r.len) {
-            const uint64_t v0 = (r.off + mis) & ~15ull;
-            n_tiles += (r.off + mis + r.len - v0 + kPhTile - 1) / kPhTile;
-        }
-        if (n_tiles >= 0xFFFFFFFFull || need_entries >= 0xFFFFFFFFull)
-            return invalid("rcdc_pack_header_parse: the batch may hold 2^32 - 1 entries or more");
+    std::vector<uint32_t> tile_first;
+    switch (tile_table(refs, n_headers, plain_len, d_plain, kPhTile, tile_first, n_tiles,
+                       [&](uint64_t len) {
+        need_entries += rcdc_pack_header_parse_bound(len);
+        return need_entries < 0xFFFFFFFFull;
+    })) {
+    case TileTable::RefOutside:
+        return invalid("rcdc_pack_header_parse: a ref lies outside the arena");
+    case TileTable::ArenaNull: return invalid("rcdc_pack_header_parse: d_plain is NULL");
+    case TileTable::TooMany:
+        return invalid("rcdc_pack_header_parse: the batch may hold 2^32 - 1 entries or more");
+    case TileTable::Ok: break;
     }
-    tile_first[n_headers] = (uint32_t)n_tiles;
     if (cap_entries < need_entries)
         return invalid("rcdc_pack_header_parse: cap_entries below rcdc_pack_header_parse_bound");
     for (int t = 0; t < 2 && n_headers; t++)

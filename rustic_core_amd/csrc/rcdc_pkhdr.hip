@@ -49,41 +49,11 @@
 // both to consecutive addresses.
 
 #include "rcdc_pkhdr.h"
+#include "rcdc_wave.h"
 
 namespace {
 
 using namespace rcdc;
-
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_incl_add64(uint64_t v) {
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)v, d, 64);
-        const uint32_t hi = __shfl_up((uint32_t)(v >> 32), d, 64);
-        if (lane >= d) v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t src) {
-    const uint32_t lo = __shfl((uint32_t)v, src, 64);
-    const uint32_t hi = __shfl((uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 
 // The header of tile t (uniform over the wave): the last h with tile_first[h] <= t.
 __device__ __forceinline__ uint32_t header_of_tile(const PhArgs &a, uint32_t t) {
@@ -137,28 +107,6 @@ __device__ __forceinline__ uint32_t walk_n(uint32_t p) { return (p >> 6) & 63u; 
 __device__ __forceinline__ uint32_t walk_tree(uint32_t p) { return (p >> 12) & 63u; }
 __device__ __forceinline__ uint32_t walk_err(uint32_t p) { return (p >> 18) & 3u; }
 __device__ __forceinline__ uint32_t walk_pos(uint32_t p) { return (p >> 20) & 2047u; }
-
-// One workgroup of 1024, a record of four uint32 per thread: the sum of the
-// records of the threads before this one, and *all: of all 1024.
-__device__ u32x4v block_excl4(u32x4v x, u32x4v *lds /* 16 */, u32x4v *all) {
-    const uint32_t lane = lane_id(), wave = threadIdx.x / 64;
-    u32x4v inc;
-    inc.x = wave_incl_add(x.x);
-    inc.y = wave_incl_add(x.y);
-    inc.z = wave_incl_add(x.z);
-    inc.w = wave_incl_add(x.w);
-    __syncthreads();  // a call before this one has read lds
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    u32x4v before = {0u, 0u, 0u, 0u}, sum = {0u, 0u, 0u, 0u};
-    for (uint32_t w = 0; w < 16; w++) {
-        const u32x4v s = lds[w];
-        if (w < wave) before += s;
-        sum += s;
-    }
-    *all = sum;
-    return before + inc - x;
-}
 
 }  // namespace
 
@@ -316,19 +264,7 @@ __global__ __launch_bounds__(1024) void rcdc_ph_number_kernel(PhArgs a) {
 // exclusive scan of the workgroups' sums in place, the totals behind them
 __global__ __launch_bounds__(1024) void rcdc_ph_number_scan_kernel(PhArgs a) {
     __shared__ u32x4v lds[16];
-    u32x4v *v = reinterpret_cast<u32x4v *>(a.add_sums);
-    const uint32_t n = (a.n_headers + kPhScan - 1) / kPhScan;
-    u32x4v carry = {0u, 0u, 0u, 0u};
-    for (uint32_t base = 0; base < n; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        u32x4v x = {0u, 0u, 0u, 0u};
-        if (i < n) x = v[i];
-        u32x4v all;
-        const u32x4v before = block_excl4(x, lds, &all);
-        if (i < n) v[i] = carry + before;
-        carry += all;
-    }
-    if (threadIdx.x == 0) v[n] = carry;
+    block_scan4(reinterpret_cast<u32x4v *>(a.add_sums), (a.n_headers + kPhScan - 1) / kPhScan, lds);
 }
 
 // the sums added back, adds[n_headers] (the totals), and the headers' records
@@ -419,24 +355,16 @@ __global__ __launch_bounds__(256) void rcdc_ph_emit_kernel(PhArgs a) {
 
 namespace rcdc {
 
-static inline uint32_t ph_blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
-#define PH_LAUNCH(kernel, grid, block, ...)                                        \
-    do {                                                                           \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);   \
-        if (hipError_t e_ = hipGetLastError(); e_ != hipSuccess) return e_;        \
-    } while (0)
-
 hipError_t launch_ph_parse(const PhArgs &a, hipStream_t st) {
     if (a.n_tiles)
-        PH_LAUNCH(rcdc_ph_walk_kernel, ph_blocks(a.n_tiles, kPhBlock / 64), kPhBlock, a);
-    PH_LAUNCH(rcdc_ph_chain_kernel, a.n_headers, 64, a);
-    const uint32_t scans = ph_blocks(a.n_headers, kPhScan);
-    PH_LAUNCH(rcdc_ph_number_kernel, scans, kPhScan, a);
-    PH_LAUNCH(rcdc_ph_number_scan_kernel, 1, 1024, a);
-    PH_LAUNCH(rcdc_ph_number_apply_kernel, scans, kPhScan, a);
+        RCDC_LAUNCH(rcdc_ph_walk_kernel, blocks(a.n_tiles, kPhBlock / 64), kPhBlock, a);
+    RCDC_LAUNCH(rcdc_ph_chain_kernel, a.n_headers, 64, a);
+    const uint32_t scans = blocks(a.n_headers, kPhScan);
+    RCDC_LAUNCH(rcdc_ph_number_kernel, scans, kPhScan, a);
+    RCDC_LAUNCH(rcdc_ph_number_scan_kernel, 1, 1024, a);
+    RCDC_LAUNCH(rcdc_ph_number_apply_kernel, scans, kPhScan, a);
     if (a.n_tiles)
-        PH_LAUNCH(rcdc_ph_emit_kernel, ph_blocks(a.n_tiles, kPhBlock / 64), kPhBlock, a);
+        RCDC_LAUNCH(rcdc_ph_emit_kernel, blocks(a.n_tiles, kPhBlock / 64), kPhBlock, a);
     return hipSuccess;
 }
 

@@ -16,26 +16,6 @@
 
 using namespace rcdc;
 
-namespace {
-
-// device allocations of one call
-struct Scratch {
-    std::vector<void *> ptrs;
-    ~Scratch() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t get(T **out, uint64_t n) {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, (n ? n : 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(p);
-        *out = static_cast<T *>(p);
-        return e;
-    }
-};
-
-}  // namespace
-
 extern "C" {
 
 void rcdc_tree_parse_bound(uint64_t len, uint64_t *max_data_ids, uint64_t *max_tree_ids,
@@ -75,29 +55,23 @@ rcdc_status tree_parse(const char *fn, bool nodes, rcdc_ctx *ctx, const void *d_
     if (nodes && n_blobs && !d_nodes) return fail("d_nodes is NULL");
     uint64_t need_nodes = 0;
     uint64_t need_data = 0, need_tree = 0, n_tiles = 0, bytes = 0;
-    std::vector<uint32_t> tile_first(n_blobs + 1u, 0u);
-    const uint64_t mis = (uint64_t)(uintptr_t)d_text & 15u;
-    for (uint32_t b = 0; b < n_blobs; b++) {
-        const rcdc_trparse_ref r = refs[b];
-        if (r.off > text_len || r.len > text_len - r.off)
-            return fail("a ref lies outside the arena");
-        if (r.len && !d_text) return fail("d_text is NULL");
+    std::vector<uint32_t> tile_first;
+    switch (tile_table(refs, n_blobs, text_len, d_text, kTrTile, tile_first, n_tiles,
+                       [&](uint64_t len) {
         uint64_t d = 0, t = 0, nn = 0;
-        rcdc_tree_parse_bound(r.len, &d, &t, &nn);
+        rcdc_tree_parse_bound(len, &d, &t, &nn);
         need_data += d;
         need_tree += t;
         need_nodes += nn;
-        bytes += r.len;
-        tile_first[b] = (uint32_t)n_tiles;
-        if (r.len) {
-            const uint64_t v0 = (r.off + mis) & ~15ull;
-            n_tiles += (r.off + mis + r.len - v0 + kTrTile - 1) / kTrTile;
-        }
+        bytes += len;
         // every count of the structural pass is a count of bytes
-        if (n_tiles >= 0xFFFFFFFFull || bytes >= 0xFFFFFFFFull)
-            return fail("the batch holds 2^32 - 1 bytes or more");
+        return bytes < 0xFFFFFFFFull;
+    })) {
+    case TileTable::RefOutside: return fail("a ref lies outside the arena");
+    case TileTable::ArenaNull: return fail("d_text is NULL");
+    case TileTable::TooMany: return fail("the batch holds 2^32 - 1 bytes or more");
+    case TileTable::Ok: break;
     }
-    tile_first[n_blobs] = (uint32_t)n_tiles;
     if ((d_data_ids && cap_data_ids < need_data) ||
         ((d_tree_ids || d_tree_is_dir) && cap_tree_ids < need_tree) ||
         (nodes && cap_nodes < need_nodes))
@@ -137,17 +111,17 @@ rcdc_status tree_parse(const char *fn, bool nodes, rcdc_ctx *ctx, const void *d_
     HIP_TRY(hipMemcpyAsync(&a.total, a.counts + n_tiles, sizeof a.total, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
 
-    HIP_TRY(sc.get(&a.node_open, a.total.nodes));
-    HIP_TRY(sc.get(&a.id_open, a.total.ids));
-    HIP_TRY(sc.get(&a.c4, a.total.c4));
-    HIP_TRY(sc.get(&a.c2, a.total.c2));
-    HIP_TRY(sc.get(&a.tmp_ids, (uint64_t)a.total.ids * 32));
-    HIP_TRY(sc.get(&a.tmp_nodes, a.total.nodes));
+    HIP_TRY(sc.get(&a.node_open, a.total.n[kTrNode]));
+    HIP_TRY(sc.get(&a.id_open, a.total.n[kTrId]));
+    HIP_TRY(sc.get(&a.c4, a.total.n[kTrC4]));
+    HIP_TRY(sc.get(&a.c2, a.total.n[kTrC2]));
+    HIP_TRY(sc.get(&a.tmp_ids, (uint64_t)a.total.n[kTrId] * 32));
+    HIP_TRY(sc.get(&a.tmp_nodes, a.total.n[kTrNode]));
     uint32_t *adds = nullptr;
-    HIP_TRY(sc.get(&adds, ((uint64_t)a.total.nodes + 1) * 4));
+    HIP_TRY(sc.get(&adds, ((uint64_t)a.total.n[kTrNode] + 1) * 4));
     a.adds = adds;
     uint32_t *add_sums = nullptr;
-    HIP_TRY(sc.get(&add_sums, ((uint64_t)a.total.nodes / kTrScan + 2) * 4));
+    HIP_TRY(sc.get(&add_sums, ((uint64_t)a.total.n[kTrNode] / kTrScan + 2) * 4));
     a.add_sums = add_sums;
     HIP_TRY(sc.get(&a.blobs, n_blobs));
     a.data_ids = static_cast<uint8_t *>(d_data_ids);
@@ -163,7 +137,7 @@ rcdc_status tree_parse(const char *fn, bool nodes, rcdc_ctx *ctx, const void *d_
     }
     HIP_TRY(launch_tr_parse(a, st));
     uint32_t tot[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(tot, adds + (uint64_t)a.total.nodes * 4, sizeof tot,
+    HIP_TRY(hipMemcpyAsync(tot, adds + (uint64_t)a.total.n[kTrNode] * 4, sizeof tot,
                           hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(blobs, a.blobs, n_blobs * sizeof *blobs, hipMemcpyDeviceToHost, st));
     if (nodes)

@@ -5,47 +5,34 @@
 #include <stdint.h>
 
 #include "../../include/rcdc.h"
+#include "rcdc_json_tiles.h"
 
 namespace rcdc {
 
-constexpr uint32_t kTrTile = RCDC_TRPARSE_TILE;  // bytes per tile: one wave, kTrRows rows
-constexpr uint32_t kTrRow = 64 * 16;             // one 16-byte load per lane
-constexpr uint32_t kTrRows = kTrTile / kTrRow;
+constexpr uint32_t kTrTile = RCDC_TRPARSE_TILE;  // bytes per tile: one wave
 constexpr uint32_t kTrBlock = 256;               // 4 tiles per workgroup
 constexpr uint32_t kTrScan = 1024;               // node records per workgroup of the numbering's scan
 
-// A tile as a function of the string state at its first byte (whether that
-// byte is escaped is known before, TrArgs::esc): the parity of its quotes
-// that count, and the change of depth when it starts outside (d0) or inside
-// (d1) a string.
-struct TrTileSum {
-    int32_t d0, d1;
-    uint32_t q;
+// The structural pass's records (rcdc_json_tiles.h).  The event kinds, in
+// the order of TileCounts::n: node opens ('{' at depth 2), string opens at
+// depth 4 (the elements of "content"), ']' at depth 4 (closes "content" or
+// "extended_attributes") and ']' at depth 2 (closes "nodes").
+enum TrEvent : uint32_t { kTrNode, kTrId, kTrC4, kTrC2 };
+struct TrGrammar {
+    // ch is a byte that counts, outside a string; -1: no event
+    RCDC_JT_FN static int event_of(uint8_t ch, int32_t depth) {
+        if (ch == '{') return depth == 2 ? (int)kTrNode : -1;
+        if (ch == '"') return depth == 4 ? (int)kTrId : -1;
+        if (ch == ']') return depth == 4 ? (int)kTrC4 : depth == 2 ? (int)kTrC2 : -1;
+        return -1;
+    }
 };
-// The state at a tile's first byte.
-struct TrTileIn {
-    uint32_t instr;
-    int32_t depth;
-};
-// Per tile, then (after the scan) before the tile: node opens ('{' at depth
-// 2), string opens at depth 4 (the elements of "content"), ']' at depth 4
-// (closes "content" or "extended_attributes") and ']' at depth 2 (closes
-// "nodes").
-struct TrCounts {
-    uint32_t nodes, ids, c4, c2;
-};
-struct TrIdOpen {
-    uint64_t pos;
-    uint32_t blob, pad;
-};
-struct TrNodeOpen {
-    uint64_t pos;
-    uint32_t blob, id_rank, c4_rank, pad;
-};
-struct TrClose {
-    uint64_t pos;
-    uint32_t blob, rank;  // id opens (c4) / node opens (c2) before it
-};
+using TrTileSum = jt::TileSum;
+using TrTileIn = jt::TileIn;
+using TrCounts = jt::TileCounts;
+using TrIdOpen = jt::TileOpen;          // ref: the blob
+using TrNodeOpen = jt::TileOpenRanked;  // rank_a: id opens, rank_b: ']' at depth 4 before it
+using TrClose = jt::TileClose;          // rank: id opens (c4) / node opens (c2) before it
 constexpr uint32_t kTrNodeOk = 1u, kTrNodeFile = 2u, kTrNodeDir = 4u, kTrNodeSubtree = 8u;
 // for the node records of rcdc_tree_nodes: "content" is an array, the raw
 // name holds a backslash, and the type as its index in NODE_TYPES

@@ -5,24 +5,10 @@
 // rcdc_tree_nodes is the same kernels with TrArgs::gn set (the grammar G_N)
 // and one more at the end, which writes a record per node.
 //
-// The structural pass.  A byte is ESCAPED when an odd run of backslashes ends
-// right before it; an escaped byte and a backslash that is not escaped count
-// for nothing, every other quote toggles the string state, and the nesting
-// depth is the count of brackets outside strings.  Whether a byte is escaped
-// depends on the bytes before it alone, not on the string state, so it is
-// settled first: a tile (kTrTile bytes, one wave, 16 bytes per lane and row)
-// looks back from its first byte over the backslash run before it, one tile
-// at most (a longer run marks the blob), and inside a row every lane learns
-// the parity of the run that ends before its chunk from two ballots (a chunk
-// of 16 backslashes hands the parity on, any other chunk sets it).  From
-// there the pass is G's: a tile is summarised as a function of the string
-// state at its first byte (TrTileSum); one wave per blob scans its tiles'
-// functions into states (TrTileIn); with the state known, the tiles count and
-// then write, in order of position, the four kinds of byte the strict lanes
-// start from or jump to: '{' at depth 2 (a node), '"' opening a string at
-// depth 4 (an element of "content"), ']' at depth 4 (ends "content" or
-// "extended_attributes"), ']' at depth 2 (ends "nodes").  The pass validates
-// nothing.
+// The structural pass is rcdc_json_tiles.h's with ESC true.  The four kinds
+// of byte it records: '{' at depth 2 (a node), '"' opening a string at depth 4
+// (an element of "content"), ']' at depth 4 (ends "content" or
+// "extended_attributes"), ']' at depth 2 (ends "nodes").
 //
 // The strict lanes, one lane each.  Every byte of a blob in G_T is checked by
 // exactly one lane:
@@ -35,11 +21,8 @@
 //                 after it up to the next node's '{' or the ']' of "nodes";
 //   the blob lane the root object without the nodes, and what surrounds it.
 // A lane accepts only strings whose escapes are JSON's, so its parse follows
-// the same quotes and brackets as the structural pass: where a lane expects
-// the next id or node to begin, the pass has recorded an open of that kind and
-// a lane of its own checks it; the recorded ']' is the one the chain of those
-// lanes ends at.  Any lane that fails marks its blob, and a marked blob is
-// NOT_PARSED: nothing of it is written.
+// the same quotes and brackets as the structural pass.  Any lane that fails
+// marks its blob, and a marked blob is NOT_PARSED: nothing of it is written.
 //
 // Numbering.  The node records (content ids of "file" nodes, subtrees, nodes;
 // zero for a blob that is not OK) are scanned into positions, a workgroup per
@@ -52,277 +35,21 @@
 namespace {
 
 using namespace rcdc;
+using namespace rcdc::jt;
 
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+static_assert(kTrBlock == kTileBlock, "the structural kernels run kTileBlock threads");
 
-// ---- wave helpers -----------------------------------------------------------
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// g after f, both TrTileSum
-__device__ __forceinline__ TrTileSum compose(const TrTileSum &f, const TrTileSum &g) {
-    TrTileSum r;
-    r.q = f.q ^ g.q;
-    r.d0 = f.d0 + (f.q ? g.d1 : g.d0);
-    r.d1 = f.d1 + (f.q ? g.d0 : g.d1);
-    return r;
-}
-
-__device__ __forceinline__ TrTileSum wave_incl_compose(TrTileSum v) {
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        TrTileSum o;
-        o.d0 = __shfl_up(v.d0, d, 64);
-        o.d1 = __shfl_up(v.d1, d, 64);
-        o.q = __shfl_up(v.q, d, 64);
-        if (lane >= d) v = compose(o, v);
-    }
-    return v;
-}
-
-__device__ __forceinline__ TrTileIn apply(const TrTileIn &s, const TrTileSum &f) {
-    TrTileIn r;
-    r.instr = s.instr ^ f.q;
-    r.depth = s.depth + (s.instr ? f.d1 : f.d0);
-    return r;
-}
-
-// ---- a tile's bytes ------------------------------------------------------------
-
-// The blob of tile t (uniform over the wave): the last b with tile_first[b] <= t.
-__device__ __forceinline__ uint32_t blob_of_tile(const TrArgs &a, uint32_t t) {
-    uint32_t lo = 0, hi = a.n_blobs;  // tile_first[lo] <= t < tile_first[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (a.tile_first[mid] <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-struct Chunk {
-    uint8_t b[16];
-    uint32_t valid;   // bit j: byte j belongs to the blob
-    uint64_t pos;     // arena offset of byte 0 (may wrap below 0 for the arena's first chunk)
-};
-
-// The 16 bytes of this lane in row `row` of tile `k` of the blob [lo, hi).
-// Chunks are 16-byte aligned addresses; one that lies wholly in the arena is
-// one dword x4 load, the arena's ragged first and last chunk go byte by byte.
-// Bytes outside the blob read as spaces.
-__device__ __forceinline__ Chunk load_chunk(const TrArgs &a, uint64_t lo, uint64_t hi, uint32_t k,
-                                            uint32_t row) {
-    const uint64_t mis = (uint64_t)(uintptr_t)a.text & 15u;
-    const uint64_t v0 = (lo + mis) & ~15ull;  // in "arena offset + mis": aligned when a multiple of 16
-    const uint64_t v = v0 + (uint64_t)k * kTrTile + (uint64_t)row * kTrRow + lane_id() * 16u;
-    Chunk c;
-    c.pos = v - mis;
-    c.valid = 0;
-    // the chunk's bytes [from, to) are the blob's
-    const int64_t s = (int64_t)v - (int64_t)mis;
-    const int64_t from = (int64_t)lo > s ? (int64_t)lo - s : 0;
-    const int64_t to = (int64_t)hi - s < 16 ? (int64_t)hi - s : 16;
-    if (to <= from) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) c.b[j] = ' ';
-        return c;
-    }
-    c.valid = ((1u << to) - 1u) & ~((1u << from) - 1u);
-    if (s >= 0 && (uint64_t)s + 16u <= a.text_len) {
-        const u32x4v w = *reinterpret_cast<const u32x4v *>(a.text + s);
-        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int j = 0; j < 16; j++)
-            c.b[j] = ((c.valid >> j) & 1u) ? (uint8_t)(ws[j >> 2] >> ((j & 3) * 8)) : (uint8_t)' ';
-    } else {
-#pragma unroll
-        for (int j = 0; j < 16; j++)
-            c.b[j] = ((c.valid >> j) & 1u) ? a.text[s + j] : (uint8_t)' ';
-    }
-    return c;
-}
-
-// Whether the first byte of tile k (k >= 1) of the blob [lo, hi) is escaped:
-// the parity of the backslash run before it.  *too_long: the run has more
-// than kTrTile bytes.  Uniform over the wave.
-__device__ __forceinline__ uint32_t tile_esc(const TrArgs &a, uint64_t lo, uint32_t k,
-                                             bool *too_long) {
-    *too_long = false;
-    if (k == 0) return 0u;
-    const uint64_t mis = (uint64_t)(uintptr_t)a.text & 15u;
-    const uint64_t p = ((lo + mis) & ~15ull) + (uint64_t)k * kTrTile - mis;  // > lo
-    uint32_t run = 0;
-    while (run <= kTrTile && p - run > lo && a.text[p - 1 - run] == '\\') run++;
-    *too_long = run > kTrTile;
-    return run & 1u;
-}
-
-// Whether this lane's chunk starts escaped, given that for the row's first
-// byte (row_in); *row_out: the same for the byte after the row.
-__device__ __forceinline__ uint32_t lane_esc(const Chunk &c, uint32_t row_in, uint32_t *row_out) {
-    uint32_t tb = 0;  // backslashes at the chunk's end
-#pragma unroll
-    for (int j = 15; j >= 0; j--) {
-        if (c.b[j] != '\\') break;
-        tb++;
-    }
-    const uint64_t sets = ~__ballot(tb == 16u);  // lanes that set the parity; the others hand it on
-    const uint64_t par = __ballot(tb & 1u);
-    const uint64_t before = sets & ((1ull << lane_id()) - 1ull);
-    *row_out = sets ? (uint32_t)(par >> (63 - __clzll((long long)sets))) & 1u : row_in;
-    return before ? (uint32_t)(par >> (63 - __clzll((long long)before))) & 1u : row_in;
-}
-
-__device__ __forceinline__ int bracket(uint8_t c) {
-    return (c == '{' || c == '[') ? 1 : (c == '}' || c == ']') ? -1 : 0;
-}
-
-__device__ __forceinline__ TrTileSum chunk_sum(const Chunk &c, uint32_t esc) {
-    TrTileSum s = {0, 0, 0u};
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        if (!((c.valid >> j) & 1u)) continue;
-        const uint8_t ch = c.b[j];
-        if (esc) {
-            esc = 0u;
-        } else if (ch == '\\') {
-            esc = 1u;
-        } else if (ch == '"') {
-            s.q ^= 1u;
-        } else {
-            const int d = bracket(ch);
-            if (s.q) s.d1 += d; else s.d0 += d;
-        }
-    }
-    return s;
-}
-
-// The state at this lane's chunk, given the state `in` at the row's first
-// byte; *total: the row as a function.
-__device__ __forceinline__ TrTileIn lane_state(const TrTileIn &in, const TrTileSum &mine,
-                                               TrTileSum *total) {
-    const TrTileSum inc = wave_incl_compose(mine);
-    TrTileSum ex;
-    ex.d0 = __shfl_up(inc.d0, 1, 64);
-    ex.d1 = __shfl_up(inc.d1, 1, 64);
-    ex.q = __shfl_up(inc.q, 1, 64);
-    if (lane_id() == 0) ex = TrTileSum{0, 0, 0u};
-    total->d0 = __shfl(inc.d0, 63, 64);
-    total->d1 = __shfl(inc.d1, 63, 64);
-    total->q = __shfl(inc.q, 63, 64);
-    return apply(in, ex);
-}
-
-// kinds of event: 0 node open, 1 id open, 2 ']' at depth 4, 3 ']' at depth 2; -1 none.
-// ch is a byte that counts, outside a string.
-__device__ __forceinline__ int event_of(uint8_t ch, int32_t depth) {
-    if (ch == '{') return depth == 2 ? 0 : -1;
-    if (ch == '"') return depth == 4 ? 1 : -1;
-    if (ch == ']') return depth == 4 ? 2 : depth == 2 ? 3 : -1;
-    return -1;
-}
-
-__device__ __forceinline__ void chunk_counts(const Chunk &c, uint32_t esc, TrTileIn s,
-                                             uint32_t n[4]) {
-    n[0] = n[1] = n[2] = n[3] = 0;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        if (!((c.valid >> j) & 1u)) continue;
-        const uint8_t ch = c.b[j];
-        if (esc) {
-            esc = 0u;
-        } else if (ch == '\\') {
-            esc = 1u;
-        } else if (s.instr) {
-            if (ch == '"') s.instr = 0u;
-        } else {
-            const int e = event_of(ch, s.depth);
-            if (e >= 0) n[e]++;
-            if (ch == '"') s.instr = 1u;
-            s.depth += bracket(ch);
-        }
-    }
+__device__ __forceinline__ Tiles<rcdc_trparse_ref> tiles(const TrArgs &a) {
+    return {a.text, a.text_len, a.refs, a.tile_first, a.n_blobs, a.n_tiles,
+            kTrTile, a.sums,    a.ins,  a.counts,     a.esc,     a.blob_bad};
 }
 
 // ---- strict parsers ----------------------------------------------------------
 
-struct Cur {
-    const uint8_t *j;
-    uint64_t pos, end;
-    __device__ __forceinline__ int peek() const { return pos < end ? (int)j[pos] : -1; }
-    __device__ __forceinline__ bool eat(int c) {
-        if (peek() != c) return false;
-        pos++;
-        return true;
-    }
-    __device__ __forceinline__ void ws() {
-        while (pos < end) {
-            const uint8_t c = j[pos];
-            if (c != ' ' && c != '\t' && c != '\n' && c != '\r') break;
-            pos++;
-        }
-    }
-    // the n bytes of s, or nothing consumed
-    __device__ __forceinline__ bool lit(const char *s, uint32_t n) {
-        if (end - pos < n) return false;
-        for (uint32_t i = 0; i < n; i++)
-            if (j[pos + i] != (uint8_t)s[i]) return false;
-        pos += n;
-        return true;
-    }
-};
-
-__device__ __forceinline__ int hexval(int c) {
-    if (c >= '0' && c <= '9') return c - '0';
-    if (c >= 'a' && c <= 'f') return c - 'a' + 10;
-    if (c >= 'A' && c <= 'F') return c - 'A' + 10;
-    return -1;
-}
-
-// "<64 hex digits>" -> 32 bytes as 8 little-endian words (memory order)
-__device__ bool parse_id(Cur &c, uint32_t id[8]) {
-    if (!c.eat('"')) return false;
-    if (c.end - c.pos < 65) return false;
-    for (int w = 0; w < 8; w++) {
-        uint32_t v = 0;
-        for (int b = 0; b < 4; b++) {
-            const int h = hexval(c.j[c.pos]), l = hexval(c.j[c.pos + 1]);
-            if ((h | l) < 0) return false;
-            v |= (uint32_t)(h * 16 + l) << (b * 8);
-            c.pos += 2;
-        }
-        id[w] = v;
-    }
-    return c.eat('"');
-}
-
-// an integer of G_T of at most `max`; what follows it is the caller's to check
-__device__ bool parse_uint(Cur &c, uint64_t max) {
-    int ch = c.peek();
-    if (ch < '0' || ch > '9') return false;
-    c.pos++;
-    uint64_t v = (uint64_t)(ch - '0');
-    const bool zero = ch == '0';
-    for (;;) {
-        ch = c.peek();
-        if (ch < '0' || ch > '9') break;
-        if (zero) return false;  // a leading zero
-        const uint64_t d = (uint64_t)(ch - '0');
-        if (v > (max - d) / 10u) return false;
-        v = v * 10u + d;
-        c.pos++;
-    }
-    return true;
+// an integer of G_T of at most `max`: only that it is one
+__device__ __forceinline__ bool parse_uint_to(Cur &c, uint64_t max) {
+    uint64_t v;
+    return parse_uint(c, max, &v);
 }
 
 // n continuation bytes, the first of them in [lo, hi]
@@ -383,49 +110,6 @@ __device__ __forceinline__ bool parse_null_or_string(Cur &c) {
     return c.lit("null", 4) || parse_string(c);
 }
 
-// after a member's value: true with *more when a ',' and the next key's quote
-// follow, true with !*more when the object's '}' does
-__device__ __forceinline__ bool after_value(Cur &c, bool *more) {
-    c.ws();
-    if (c.eat(',')) {
-        c.ws();
-        *more = true;
-        return true;
-    }
-    *more = false;
-    return c.eat('}');
-}
-
-// after an element of an array: ws, then ',' ws and the next element's first
-// byte `open` (left to its own lane), or the array's ']' (left to the lane
-// that owns it)
-__device__ __forceinline__ bool after_element(Cur &c, int open) {
-    c.ws();
-    if (c.eat(',')) {
-        c.ws();
-        return c.peek() == open;
-    }
-    return c.peek() == ']';
-}
-
-// At the '[' of an array whose elements begin with `open` and have lanes of
-// their own, and whose ']' the structural pass recorded as cl[k] (of the same
-// blob): '[' ws, then the first element's first byte or the ']' itself; the
-// cursor goes on after the ']'.
-__device__ bool skip_array(Cur &c, int open, const TrClose *cl, uint32_t k, uint32_t n,
-                           uint32_t blob, uint32_t *rank) {
-    if (!c.eat('[')) return false;
-    c.ws();
-    const int ch = c.peek();
-    if (ch != open && ch != ']') return false;
-    if (k >= n) return false;
-    const TrClose r = cl[k];
-    if (r.blob != blob || r.pos < c.pos || r.pos >= c.end) return false;
-    *rank = r.rank;
-    c.pos = r.pos + 1;
-    return true;
-}
-
 // {"name": string, "value": null | string}
 __device__ bool parse_xattr(Cur &c) {
     if (!c.eat('{')) return false;
@@ -483,7 +167,7 @@ __device__ bool parse_node(const TrArgs &a, Cur &c, const TrNodeOpen &r, TrNodeT
     if (!c.eat('{')) return false;
     c.ws();
     uint32_t seen = 0, type = 0;
-    uint32_t c4 = r.c4_rank;  // the next ']' at depth 4 of this node
+    uint32_t c4 = r.rank_b;  // the next ']' at depth 4 of this node
     bool symlink = false;
     for (bool more = true; more;) {
         if (!c.eat('"')) return false;
@@ -518,21 +202,22 @@ __device__ bool parse_node(const TrArgs &a, Cur &c, const TrNodeOpen &r, TrNodeT
             else ok = false;
             break;
         case K_MODE: case K_UID: case K_GID:
-            ok = c.lit("null", 4) || parse_uint(c, 0xFFFFFFFFull);
+            ok = c.lit("null", 4) || parse_uint_to(c, 0xFFFFFFFFull);
             break;
         case K_MTIME: case K_ATIME: case K_CTIME: case K_USER: case K_GROUP: case K_LINKTARGET_RAW:
             ok = parse_null_or_string(c);
             break;
         case K_INODE: case K_DEVICE_ID: case K_SIZE: case K_LINKS: case K_DEVICE:
-            ok = parse_uint(c, ~0ull);
+            ok = parse_uint_to(c, ~0ull);
             break;
         case K_CONTENT:
             ok = true;
             if (!c.lit("null", 4)) {
                 uint32_t rank = 0;
-                ok = skip_array(c, '"', a.c4, c4++, a.total.c4, r.blob, &rank) && rank >= r.id_rank;
-                o->id0 = r.id_rank;
-                o->nids = ok ? rank - r.id_rank : 0u;
+                ok = skip_array(c, '"', a.c4, c4++, a.total.n[kTrC4], r.ref, &rank) &&
+                     rank >= r.rank_a;
+                o->id0 = r.rank_a;
+                o->nids = ok ? rank - r.rank_a : 0u;
                 o->flags |= kTrNodeContent;
             }
             break;
@@ -580,7 +265,7 @@ __device__ bool parse_root(const TrArgs &a, Cur &c, uint32_t b) {
     c.ws();
     if (!c.lit("null", 4)) {
         uint32_t rank = 0;
-        if (!skip_array(c, '{', a.c2, fb.c2, fe.c2, b, &rank)) return false;
+        if (!skip_array(c, '{', a.c2, fb.n[kTrC2], fe.n[kTrC2], b, &rank)) return false;
     }
     c.ws();
     if (!c.eat('}')) return false;
@@ -593,105 +278,13 @@ __device__ bool parse_root(const TrArgs &a, Cur &c, uint32_t b) {
 // ---- the structural pass ------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void rcdc_tr_tile_sum_kernel(TrArgs a) {
-    const uint32_t t = blockIdx.x * (kTrBlock / 64) + threadIdx.x / 64;
-    if (t >= a.n_tiles) return;
-    const uint32_t b = blob_of_tile(a, t);
-    const uint64_t lo = a.refs[b].off, hi = lo + a.refs[b].len;
-    bool too_long;
-    uint32_t esc = tile_esc(a, lo, t - a.tile_first[b], &too_long);
-    if (lane_id() == 0) {
-        a.esc[t] = (uint8_t)esc;
-        if (too_long) a.blob_bad[b] = 1u;
-    }
-    TrTileSum tile = {0, 0, 0u};
-    for (uint32_t row = 0; row < kTrRows; row++) {
-        const Chunk c = load_chunk(a, lo, hi, t - a.tile_first[b], row);
-        uint32_t next;
-        const uint32_t mine = lane_esc(c, esc, &next);
-        TrTileSum total;
-        (void)lane_state(TrTileIn{0u, 0}, chunk_sum(c, mine), &total);
-        tile = compose(tile, total);
-        esc = next;
-    }
-    if (lane_id() == 0) a.sums[t] = tile;
+    tile_sum<true, TrGrammar>(tiles(a));
 }
 
-// one wave per blob: the state at the first byte of each of its tiles
-__global__ __launch_bounds__(64) void rcdc_tr_tile_state_kernel(TrArgs a) {
-    const uint32_t b = blockIdx.x;
-    const uint32_t t0 = a.tile_first[b], t1 = a.tile_first[b + 1];
-    TrTileIn carry = {0u, 0};
-    for (uint32_t base = t0; base < t1; base += 64) {
-        const uint32_t t = base + lane_id();
-        TrTileSum mine = {0, 0, 0u};
-        if (t < t1) mine = a.sums[t];
-        TrTileSum total;
-        const TrTileIn in = lane_state(carry, mine, &total);
-        if (t < t1) a.ins[t] = in;
-        carry = apply(carry, total);
-    }
-}
+__global__ __launch_bounds__(64) void rcdc_tr_tile_state_kernel(TrArgs a) { tile_state(tiles(a)); }
 
 __global__ __launch_bounds__(256) void rcdc_tr_tile_count_kernel(TrArgs a) {
-    const uint32_t t = blockIdx.x * (kTrBlock / 64) + threadIdx.x / 64;
-    if (t >= a.n_tiles) return;
-    const uint32_t b = blob_of_tile(a, t);
-    const uint64_t lo = a.refs[b].off, hi = lo + a.refs[b].len;
-    TrTileIn in = a.ins[t];
-    uint32_t esc = a.esc[t];
-    uint32_t sum[4] = {0, 0, 0, 0};
-    for (uint32_t row = 0; row < kTrRows; row++) {
-        const Chunk c = load_chunk(a, lo, hi, t - a.tile_first[b], row);
-        uint32_t next;
-        const uint32_t mine = lane_esc(c, esc, &next);
-        TrTileSum total;
-        const TrTileIn s = lane_state(in, chunk_sum(c, mine), &total);
-        uint32_t n[4];
-        chunk_counts(c, mine, s, n);
-        for (int e = 0; e < 4; e++) sum[e] += n[e];
-        in = apply(in, total);
-        esc = next;
-    }
-    for (int e = 0; e < 4; e++) sum[e] = __shfl(wave_incl_add(sum[e]), 63, 64);
-    if (lane_id() == 0) a.counts[t] = TrCounts{sum[0], sum[1], sum[2], sum[3]};
-}
-
-// One workgroup of 1024, a record of four uint32 per thread: the sum of the
-// records of the threads before this one, and *all: of all 1024.
-__device__ u32x4v block_excl4(u32x4v x, u32x4v *lds /* 16 */, u32x4v *all) {
-    const uint32_t lane = lane_id(), wave = threadIdx.x / 64;
-    u32x4v inc;
-    inc.x = wave_incl_add(x.x);
-    inc.y = wave_incl_add(x.y);
-    inc.z = wave_incl_add(x.z);
-    inc.w = wave_incl_add(x.w);
-    __syncthreads();  // a call before this one has read lds
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    u32x4v before = {0u, 0u, 0u, 0u}, sum = {0u, 0u, 0u, 0u};
-    for (uint32_t w = 0; w < 16; w++) {
-        const u32x4v s = lds[w];
-        if (w < wave) before += s;
-        sum += s;
-    }
-    *all = sum;
-    return before + inc - x;
-}
-
-// Exclusive scan of n records of four uint32 in place, the totals to v[n]:
-// one workgroup of 1024, a chunk of 1024 records per pass.
-__device__ void block_scan4(u32x4v *v, uint32_t n, u32x4v *lds /* 16 */) {
-    u32x4v carry = {0u, 0u, 0u, 0u};
-    for (uint32_t base = 0; base < n; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        u32x4v x = {0u, 0u, 0u, 0u};
-        if (i < n) x = v[i];
-        u32x4v all;
-        const u32x4v before = block_excl4(x, lds, &all);
-        if (i < n) v[i] = carry + before;
-        carry += all;
-    }
-    if (threadIdx.x == 0) v[n] = carry;
+    tile_count<true, TrGrammar>(tiles(a));
 }
 
 __global__ __launch_bounds__(1024) void rcdc_tr_count_scan_kernel(TrArgs a) {
@@ -700,68 +293,26 @@ __global__ __launch_bounds__(1024) void rcdc_tr_count_scan_kernel(TrArgs a) {
 }
 
 __global__ __launch_bounds__(256) void rcdc_tr_tile_emit_kernel(TrArgs a) {
-    const uint32_t t = blockIdx.x * (kTrBlock / 64) + threadIdx.x / 64;
-    if (t >= a.n_tiles) return;
-    const uint32_t b = blob_of_tile(a, t);
-    const uint64_t lo = a.refs[b].off, hi = lo + a.refs[b].len;
-    TrTileIn in = a.ins[t];
-    uint32_t esc = a.esc[t];
-    const TrCounts before = a.counts[t];
-    uint32_t at[4] = {before.nodes, before.ids, before.c4, before.c2};  // before this row
-    const uint32_t cap[4] = {a.total.nodes, a.total.ids, a.total.c4, a.total.c2};
-    for (uint32_t row = 0; row < kTrRows; row++) {
-        const Chunk c = load_chunk(a, lo, hi, t - a.tile_first[b], row);
-        uint32_t next;
-        uint32_t mine = lane_esc(c, esc, &next);
-        TrTileSum total;
-        TrTileIn s = lane_state(in, chunk_sum(c, mine), &total);
-        uint32_t n[4], my[4];
-        chunk_counts(c, mine, s, n);
-        for (int e = 0; e < 4; e++) {
-            const uint32_t inc = wave_incl_add(n[e]);
-            my[e] = at[e] + inc - n[e];
-            at[e] += __shfl(inc, 63, 64);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            if (!((c.valid >> j) & 1u)) continue;
-            const uint8_t ch = c.b[j];
-            if (mine) {
-                mine = 0u;
-            } else if (ch == '\\') {
-                mine = 1u;
-            } else if (s.instr) {
-                if (ch == '"') s.instr = 0u;
-            } else {
-                const int e = event_of(ch, s.depth);
-                const uint64_t pos = c.pos + (uint64_t)j;
-                if (e >= 0 && my[e] < cap[e]) {  // the counts of the pass before: always within
-                    if (e == 0) a.node_open[my[0]] = TrNodeOpen{pos, b, my[1], my[2], 0u};
-                    else if (e == 1) a.id_open[my[1]] = TrIdOpen{pos, b, 0u};
-                    else if (e == 2) a.c4[my[2]] = TrClose{pos, b, my[1]};
-                    else a.c2[my[3]] = TrClose{pos, b, my[0]};
-                }
-                if (e >= 0) my[e]++;
-                if (ch == '"') s.instr = 1u;
-                s.depth += bracket(ch);
-            }
-        }
-        in = apply(in, total);
-        esc = next;
-    }
+    tile_emit<true, TrGrammar>(tiles(a), a.total,
+                               [&](int e, uint64_t pos, uint32_t b, const uint32_t *my) {
+        if (e == kTrNode) a.node_open[my[kTrNode]] = TrNodeOpen{pos, b, my[kTrId], my[kTrC4], 0u};
+        else if (e == kTrId) a.id_open[my[kTrId]] = TrIdOpen{pos, b, 0u};
+        else if (e == kTrC4) a.c4[my[kTrC4]] = TrClose{pos, b, my[kTrId]};
+        else a.c2[my[kTrC2]] = TrClose{pos, b, my[kTrNode]};
+    });
 }
 
 // ---- the strict lanes ------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void rcdc_tr_id_kernel(TrArgs a) {
     const uint32_t i = blockIdx.x * kTrBlock + threadIdx.x;
-    if (i >= a.total.ids) return;
+    if (i >= a.total.n[kTrId]) return;
     const TrIdOpen r = a.id_open[i];
-    const rcdc_trparse_ref ref = a.refs[r.blob];
+    const rcdc_trparse_ref ref = a.refs[r.ref];
     Cur c = {a.text, r.pos, ref.off + ref.len};
     uint32_t id[8];
     if (!parse_id(c, id) || !after_element(c, '"')) {
-        a.blob_bad[r.blob] = 1u;
+        a.blob_bad[r.ref] = 1u;
         return;
     }
     u32x4v *d = reinterpret_cast<u32x4v *>(a.tmp_ids + (uint64_t)i * 32u);
@@ -771,18 +322,18 @@ __global__ __launch_bounds__(256) void rcdc_tr_id_kernel(TrArgs a) {
 
 __global__ __launch_bounds__(256) void rcdc_tr_node_kernel(TrArgs a) {
     const uint32_t i = blockIdx.x * kTrBlock + threadIdx.x;
-    if (i >= a.total.nodes) return;
+    if (i >= a.total.n[kTrNode]) return;
     const TrNodeOpen r = a.node_open[i];
-    const rcdc_trparse_ref ref = a.refs[r.blob];
+    const rcdc_trparse_ref ref = a.refs[r.ref];
     Cur c = {a.text, r.pos, ref.off + ref.len};
     TrNodeTmp o = {};
-    o.blob = r.blob;
+    o.blob = r.ref;
     if (parse_node(a, c, r, &o)) {
         o.flags |= kTrNodeOk;
     } else {
         o.flags = 0u;
         o.nids = 0u;
-        a.blob_bad[r.blob] = 1u;
+        a.blob_bad[r.ref] = 1u;
     }
     a.tmp_nodes[i] = o;
 }
@@ -807,7 +358,7 @@ __global__ __launch_bounds__(1024) void rcdc_tr_number_kernel(TrArgs a) {
     __shared__ u32x4v lds[16];
     const uint32_t i = blockIdx.x * kTrScan + threadIdx.x;
     u32x4v x = {0u, 0u, 0u, 0u};
-    if (i < a.total.nodes) {
+    if (i < a.total.n[kTrNode]) {
         const TrNodeTmp *p = a.tmp_nodes + i;
         if ((p->flags & kTrNodeOk) && a.blob_ok[p->blob]) {
             x.x = (p->flags & kTrNodeFile) ? p->nids : 0u;
@@ -817,13 +368,14 @@ __global__ __launch_bounds__(1024) void rcdc_tr_number_kernel(TrArgs a) {
     }
     u32x4v all;
     const u32x4v before = block_excl4(x, lds, &all);
-    if (i < a.total.nodes) reinterpret_cast<u32x4v *>(a.adds)[i] = before;
+    if (i < a.total.n[kTrNode]) reinterpret_cast<u32x4v *>(a.adds)[i] = before;
     if (threadIdx.x == 0) reinterpret_cast<u32x4v *>(a.add_sums)[blockIdx.x] = all;
 }
 
 __global__ __launch_bounds__(1024) void rcdc_tr_number_scan_kernel(TrArgs a) {
     __shared__ u32x4v lds[16];
-    block_scan4(reinterpret_cast<u32x4v *>(a.add_sums), (a.total.nodes + kTrScan - 1) / kTrScan, lds);
+    block_scan4(reinterpret_cast<u32x4v *>(a.add_sums), (a.total.n[kTrNode] + kTrScan - 1) / kTrScan,
+                lds);
 }
 
 // also adds[n]: the totals
@@ -831,16 +383,16 @@ __global__ __launch_bounds__(1024) void rcdc_tr_number_apply_kernel(TrArgs a) {
     const uint32_t i = blockIdx.x * kTrScan + threadIdx.x;
     u32x4v *adds = reinterpret_cast<u32x4v *>(a.adds);
     const u32x4v *sums = reinterpret_cast<const u32x4v *>(a.add_sums);
-    if (i < a.total.nodes) adds[i] += sums[blockIdx.x];
-    if (i == 0) adds[a.total.nodes] = sums[(a.total.nodes + kTrScan - 1) / kTrScan];
+    if (i < a.total.n[kTrNode]) adds[i] += sums[blockIdx.x];
+    if (i == 0) adds[a.total.n[kTrNode]] = sums[(a.total.n[kTrNode] + kTrScan - 1) / kTrScan];
 }
 
 __global__ __launch_bounds__(256) void rcdc_tr_blob_kernel(TrArgs a) {
     const uint32_t b = blockIdx.x * kTrBlock + threadIdx.x;
     if (b >= a.n_blobs) return;
     const u32x4v *adds = reinterpret_cast<const u32x4v *>(a.adds);
-    const u32x4v x0 = adds[a.counts[a.tile_first[b]].nodes];
-    const u32x4v x1 = adds[a.counts[a.tile_first[b + 1]].nodes];
+    const u32x4v x0 = adds[a.counts[a.tile_first[b]].n[kTrNode]];
+    const u32x4v x1 = adds[a.counts[a.tile_first[b + 1]].n[kTrNode]];
     rcdc_trparse_blob r = {};
     r.status = a.blob_ok[b] ? RCDC_TRPARSE_OK : RCDC_TRPARSE_NOT_PARSED;
     r.nodes = x1.z - x0.z;
@@ -856,7 +408,7 @@ __global__ __launch_bounds__(256) void rcdc_tr_blob_kernel(TrArgs a) {
 // the count of nodes of OK blobs before it, which the numbering scanned
 __global__ __launch_bounds__(256) void rcdc_tr_record_kernel(TrArgs a) {
     const uint32_t i = blockIdx.x * kTrBlock + threadIdx.x;
-    if (i >= a.total.nodes) return;
+    if (i >= a.total.n[kTrNode]) return;
     const TrNodeTmp *p = a.tmp_nodes + i;
     if (!(p->flags & kTrNodeOk) || !a.blob_ok[p->blob]) return;
     const u32x4v x = reinterpret_cast<const u32x4v *>(a.adds)[i];
@@ -873,7 +425,7 @@ __global__ __launch_bounds__(256) void rcdc_tr_record_kernel(TrArgs a) {
 
 __global__ __launch_bounds__(256) void rcdc_tr_subtree_kernel(TrArgs a) {
     const uint32_t i = blockIdx.x * kTrBlock + threadIdx.x;
-    if (i >= a.total.nodes) return;
+    if (i >= a.total.n[kTrNode]) return;
     const TrNodeTmp *p = a.tmp_nodes + i;
     if ((p->flags & (kTrNodeOk | kTrNodeSubtree)) != (kTrNodeOk | kTrNodeSubtree) ||
         !a.blob_ok[p->blob])
@@ -890,14 +442,14 @@ __global__ __launch_bounds__(256) void rcdc_tr_subtree_kernel(TrArgs a) {
 
 __global__ __launch_bounds__(256) void rcdc_tr_scatter_kernel(TrArgs a) {
     const uint32_t i = blockIdx.x * kTrBlock + threadIdx.x;
-    if (i >= a.total.ids) return;
+    if (i >= a.total.n[kTrId]) return;
     // the node of id i: the last node opened with id_rank <= i (nodes before
     // it with the same rank hold no id)
-    uint32_t lo = 0, hi = a.total.nodes;
-    if (hi == 0 || a.node_open[0].id_rank > i) return;
+    uint32_t lo = 0, hi = a.total.n[kTrNode];
+    if (hi == 0 || a.node_open[0].rank_a > i) return;
     while (hi - lo > 1) {
         const uint32_t mid = lo + (hi - lo) / 2;
-        if (a.node_open[mid].id_rank <= i) lo = mid; else hi = mid;
+        if (a.node_open[mid].rank_a <= i) lo = mid; else hi = mid;
     }
     const TrNodeTmp *p = a.tmp_nodes + lo;
     if ((p->flags & (kTrNodeOk | kTrNodeFile)) != (kTrNodeOk | kTrNodeFile) ||
@@ -913,41 +465,34 @@ __global__ __launch_bounds__(256) void rcdc_tr_scatter_kernel(TrArgs a) {
 
 namespace rcdc {
 
-static inline uint32_t tr_blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
-#define TR_LAUNCH(kernel, grid, block, ...)                                        \
-    do {                                                                           \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);   \
-        if (hipError_t e_ = hipGetLastError(); e_ != hipSuccess) return e_;        \
-    } while (0)
-
 hipError_t launch_tr_structure(const TrArgs &a, hipStream_t st) {
     if (a.n_tiles) {
-        TR_LAUNCH(rcdc_tr_tile_sum_kernel, tr_blocks(a.n_tiles, kTrBlock / 64), kTrBlock, a);
-        TR_LAUNCH(rcdc_tr_tile_state_kernel, a.n_blobs, 64, a);
-        TR_LAUNCH(rcdc_tr_tile_count_kernel, tr_blocks(a.n_tiles, kTrBlock / 64), kTrBlock, a);
+        RCDC_LAUNCH(rcdc_tr_tile_sum_kernel, blocks(a.n_tiles, kTrBlock / 64), kTrBlock, a);
+        RCDC_LAUNCH(rcdc_tr_tile_state_kernel, a.n_blobs, 64, a);
+        RCDC_LAUNCH(rcdc_tr_tile_count_kernel, blocks(a.n_tiles, kTrBlock / 64), kTrBlock, a);
     }
-    TR_LAUNCH(rcdc_tr_count_scan_kernel, 1, 1024, a);
+    RCDC_LAUNCH(rcdc_tr_count_scan_kernel, 1, 1024, a);
     return hipSuccess;
 }
 
 hipError_t launch_tr_parse(const TrArgs &a, hipStream_t st) {
+    const uint32_t n_ids = a.total.n[kTrId], n_nodes = a.total.n[kTrNode];
     if (a.n_tiles)
-        TR_LAUNCH(rcdc_tr_tile_emit_kernel, tr_blocks(a.n_tiles, kTrBlock / 64), kTrBlock, a);
-    if (a.total.ids) TR_LAUNCH(rcdc_tr_id_kernel, tr_blocks(a.total.ids, kTrBlock), kTrBlock, a);
-    if (a.total.nodes) TR_LAUNCH(rcdc_tr_node_kernel, tr_blocks(a.total.nodes, kTrBlock), kTrBlock, a);
-    TR_LAUNCH(rcdc_tr_root_kernel, tr_blocks(a.n_blobs, kTrBlock), kTrBlock, a);
-    const uint32_t scans = tr_blocks(a.total.nodes, kTrScan);
-    if (scans) TR_LAUNCH(rcdc_tr_number_kernel, scans, kTrScan, a);
-    TR_LAUNCH(rcdc_tr_number_scan_kernel, 1, 1024, a);
-    TR_LAUNCH(rcdc_tr_number_apply_kernel, scans ? scans : 1u, kTrScan, a);
-    TR_LAUNCH(rcdc_tr_blob_kernel, tr_blocks(a.n_blobs, kTrBlock), kTrBlock, a);
-    if (a.total.nodes)
-        TR_LAUNCH(rcdc_tr_subtree_kernel, tr_blocks(a.total.nodes, kTrBlock), kTrBlock, a);
-    if (a.total.ids && a.data_ids)
-        TR_LAUNCH(rcdc_tr_scatter_kernel, tr_blocks(a.total.ids, kTrBlock), kTrBlock, a);
-    if (a.total.nodes && a.nodes)
-        TR_LAUNCH(rcdc_tr_record_kernel, tr_blocks(a.total.nodes, kTrBlock), kTrBlock, a);
+        RCDC_LAUNCH(rcdc_tr_tile_emit_kernel, blocks(a.n_tiles, kTrBlock / 64), kTrBlock, a);
+    if (n_ids) RCDC_LAUNCH(rcdc_tr_id_kernel, blocks(n_ids, kTrBlock), kTrBlock, a);
+    if (n_nodes) RCDC_LAUNCH(rcdc_tr_node_kernel, blocks(n_nodes, kTrBlock), kTrBlock, a);
+    RCDC_LAUNCH(rcdc_tr_root_kernel, blocks(a.n_blobs, kTrBlock), kTrBlock, a);
+    const uint32_t scans = blocks(n_nodes, kTrScan);
+    if (scans) RCDC_LAUNCH(rcdc_tr_number_kernel, scans, kTrScan, a);
+    RCDC_LAUNCH(rcdc_tr_number_scan_kernel, 1, 1024, a);
+    RCDC_LAUNCH(rcdc_tr_number_apply_kernel, scans ? scans : 1u, kTrScan, a);
+    RCDC_LAUNCH(rcdc_tr_blob_kernel, blocks(a.n_blobs, kTrBlock), kTrBlock, a);
+    if (n_nodes)
+        RCDC_LAUNCH(rcdc_tr_subtree_kernel, blocks(n_nodes, kTrBlock), kTrBlock, a);
+    if (n_ids && a.data_ids)
+        RCDC_LAUNCH(rcdc_tr_scatter_kernel, blocks(n_ids, kTrBlock), kTrBlock, a);
+    if (n_nodes && a.nodes)
+        RCDC_LAUNCH(rcdc_tr_record_kernel, blocks(n_nodes, kTrBlock), kTrBlock, a);
     return hipSuccess;
 }
 
