@@ -84,6 +84,76 @@ def random_header(rng, n_max=80, bad=0.2) -> bytes:
     return h
 
 
+# ---- a pattern of very many headers, expected by arithmetic ----------------------------
+
+PATTERN = (b"", run([0]), run([1]), run([2, 2]))   # header i has shape i % 4 ...
+PATTERN_BAD = b"\x04" + run([0])[1:]               # ... but every PATTERN_EVERY-th: a bad type byte
+PATTERN_EVERY = 1000
+_COUNT = np.array([0, 1, 1, 2])
+_BLOBS = np.array([0, 100, 100, 100 + 107])        # the sum of a shape's blob lengths (``run``)
+
+
+class Pattern:
+    """``n`` headers back to back in one arena (``arena``, ``offs``,
+    ``lens``), the first four bytes of every entry's id replaced by its
+    header's number, and what rcdc_pack_header_parse gives for them by numpy
+    arithmetic: ``records`` (the fields of a PK_HEADER as int64 arrays),
+    ``ids[t]`` (n, 32) uint8 and ``locs[t]`` (n, 4) uint32 per type, ``packs``.
+    tests/test_pack_header_host.py holds it to the model at a size the model
+    handles; the device test runs it past 2^20 headers, where the model would
+    take ten seconds."""
+
+    def __init__(self, n, pack_base=(0, 0)):
+        assert PATTERN_EVERY % 4 == 0
+        i = np.arange(n)
+        shape, bad = i % 4, i % PATTERN_EVERY == PATTERN_EVERY - 1
+        self.lens = np.where(bad, len(PATTERN_BAD), np.array([len(p) for p in PATTERN])[shape])
+        self.offs = np.cumsum(self.lens) - self.lens
+        block = b"".join(PATTERN) * (PATTERN_EVERY // 4)
+        block = block[:len(block) - len(PATTERN[3])] + PATTERN_BAD
+        self.arena = np.tile(np.frombuffer(block, np.uint8), n // PATTERN_EVERY + 1)[:int(self.lens.sum())].copy()
+        # an entry's id is its last 32 bytes; its first four bytes: the header's number
+        stamp = i.astype("<u4").view(np.uint8).reshape(n, 4)
+        for at, sel in ((5, (shape == 1) | (shape == 2) | bad), (9, (shape == 3) & ~bad),
+                        (41 + 9, (shape == 3) & ~bad)):
+            self.arena[(self.offs[sel] + at)[:, None] + np.arange(4)[None, :]] = stamp[sel]
+        ok = ~bad
+        tpe = np.where(ok & (shape == 2), 1, 0)
+        count = np.where(ok, _COUNT[shape], 0)
+        number, first = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self.ids, self.locs, self.packs = [None, None], [None, None], [0, 0]
+        for t in (0, 1):
+            mine = ok & (tpe == t)
+            number[mine] = pack_base[t] + np.arange(int(mine.sum()))
+            first[mine] = np.cumsum(count[mine]) - count[mine]
+            self.packs[t] = int(mine.sum())
+            # the entries of type t in order: (header, which of its entries)
+            h = np.repeat(i[mine], count[mine])
+            k = np.arange(len(h)) - np.repeat(first[mine], count[mine])
+            two = shape[h] == 3
+            locs = np.zeros((len(h), 4), np.uint32)
+            locs[:, 0] = number[h]
+            locs[:, 1] = np.where(k == 1, 100, 0)
+            locs[:, 2] = np.where(k == 1, 107, 100)
+            locs[:, 3] = np.where(two, 1000 + k, 0)
+            ids = np.empty((len(h), 32), np.uint8)
+            ids[:] = np.frombuffer(bid(0), np.uint8)
+            ids[k == 1] = np.frombuffer(bid(1), np.uint8)
+            ids[:, :4] = stamp[h]
+            self.ids[t], self.locs[t] = ids, locs
+        z = np.zeros(n, np.int64)
+        self.records = dict(
+            status=np.where(bad, BAD_TYPE, OK), type=tpe, number=number, count=count, first=first,
+            data=np.where(tpe == 0, count, 0), tree=np.where(tpe == 1, count, 0),
+            size=np.where(ok, 32 + self.lens, 0),
+            pack_size=np.where(ok, 36 + self.lens + _BLOBS[shape], 0), err_pos=z, err_entry=z)
+
+    def headers(self):
+        """The headers as bytes, for the model."""
+        raw = self.arena.tobytes()
+        return [raw[o:o + n] for o, n in zip(self.offs.tolist(), self.lens.tolist())]
+
+
 # ---- aimed at tile boundaries ---------------------------------------------------------
 
 def sizes_to(total: int):

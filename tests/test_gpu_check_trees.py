@@ -46,21 +46,36 @@ class _Level:
             self.is_dir.append(int(tpe == D))
 
     def run(self, n_packs=(40, 40), cap=1024):
+        ids = lambda x: np.frombuffer(b"".join(x), np.uint8).reshape(-1, 32).copy()
+        hits = lambda x: np.array(x, np.int64).reshape(-1, 2)
+        want, dp, tp = model.level_rule(self.nodes, self.data_ids, self.data_hits, self.tree_ids,
+                                        self.tree_hits)
+        self.run_arrays(model.node_array(self.nodes), ids(self.data_ids), hits(self.data_hits),
+                        ids(self.tree_ids), hits(self.tree_hits), np.array(self.is_dir, np.uint8),
+                        (want, dp, tp), n_packs, cap)
+        return want, dp, tp
+
+    @staticmethod
+    def run_arrays(nodes, data_ids, data_hits, tree_ids, tree_hits, is_dir, expected,
+                   n_packs=(40, 40), cap=1024):
+        """The level over arrays: a TR_NODE array, ids (n, 32) uint8, hits
+        (n, 2) int64 of (count, pack); ``expected``: what the rule gives."""
         import torch
         from rustic_core_amd.check import run_check_level
         up = lambda a: torch.from_numpy(a).to("cuda:0")
-        ids = lambda x: up(np.frombuffer(b"".join(x), np.uint8).reshape(-1, 32).copy())
-        hits = lambda x: up(np.array([(0 if c else -1, c, p if c else -1, 0, 0, 0) for c, p in x],
-                                     np.int64).astype(np.int32).reshape(-1, 6))
+
+        def hits(x):
+            c, p = x[:, 0], x[:, 1]
+            rec = np.zeros((len(x), 6), np.int64)
+            rec[:, 0], rec[:, 1], rec[:, 2] = np.where(c != 0, 0, -1), c, np.where(c != 0, p, -1)
+            return up(rec.astype(np.int32))
         res = types.SimpleNamespace(
-            node_records=up(model.node_array(self.nodes).view(np.uint8).reshape(-1, 32).copy()),
-            data_ids=ids(self.data_ids), tree_ids=ids(self.tree_ids),
-            tree_is_dir=up(np.array(self.is_dir, np.uint8)))
+            node_records=up(nodes.view(np.uint8).reshape(-1, 32).copy()),
+            data_ids=up(data_ids), tree_ids=up(tree_ids), tree_is_dir=up(is_dir))
+        d_hits, t_hits = hits(data_hits), hits(tree_hits)
         marks = [torch.zeros(n, dtype=torch.uint8, device="cuda:0") for n in n_packs]
-        want, dp, tp = model.level_rule(self.nodes, self.data_ids, self.data_hits, self.tree_ids,
-                                        self.tree_hits)
-        n, got = run_check_level(res, hits(self.data_hits), hits(self.tree_hits), marks[0], marks[1],
-                                 cap=cap)
+        want, dp, tp = expected
+        n, got = run_check_level(res, d_hits, t_hits, marks[0], marks[1], cap=cap)
         assert n == len(want)
         assert (got is None) == (n == 0)
         if n:
@@ -69,11 +84,11 @@ class _Level:
         for m, packs, size in zip(marks, (dp, tp), n_packs):
             assert set(np.nonzero(m.cpu().numpy())[0].tolist()) == {p for p in packs if p < size}
         # the guard bytes behind exactly n findings
-        n2, flat = run_check_level(res, hits(self.data_hits), hits(self.tree_hits), marks[0], marks[1],
-                                   cap=max(n, 1), guard=GUARD)
+        n2, flat = run_check_level(res, d_hits, t_hits, marks[0], marks[1], cap=max(n, 1), guard=GUARD)
         assert n2 == n and (flat[n * 16:].cpu().numpy() == 0xA5).all()
         assert int(flat.numel()) == max(n, 1) * 16 + GUARD
-        return want, dp, tp
+        again = flat[:n * 16].cpu().numpy().view(np.uint32).reshape(-1, 4)
+        assert [tuple(r) for r in again[:, :3].tolist()] == want and not again[:, 3].any()
 
 
 def test_level_each_kind_and_the_order(gpu_ctx):
@@ -150,6 +165,66 @@ def test_level_findings_across_the_scan_blocks(gpu_ctx, n):
     want, _, _ = lv.run()
     assert len(want) == n
     lv.run(cap=n)  # room for exactly n
+
+
+def test_level_counts_past_a_round_of_sums(gpu_ctx):
+    """2^20 + 3 nodes and more than 2^21 + 5 ids: the scan of the node counts
+    has 1 025 sums and the one of the id counts more than 2 049, so the one
+    workgroup over the sums takes a second and a third round with a carry.
+    Findings stand at the first and last count of a block of 1024, of a round
+    of 2^20, and one past each; the reference is the rule in numpy
+    (tests/tree_nodes_model.py ``level_rule_np``)."""
+    n_nodes, M = (1 << 20) + 3, 1 << 20
+    k = np.arange(n_nodes)
+    nodes = np.zeros(n_nodes, model.node_array([]).dtype)
+    nodes["type"] = np.where(k % 4 == 3, D, F)
+    nodes["flags"] = np.where(k % 4 == 3, model.SUBTREE, model.CONTENT)
+    nodes["n_content"] = np.where(k % 4 == 3, 0, 3)
+    # findings of nodes: (node, type, flags, the subtree's id is null, the index holds it)
+    at_nodes = [(0, F, 0, 0, 1), (1023, D, 0, 0, 1), (1024, D, model.SUBTREE, 1, 1),
+                (M - 1, D, model.SUBTREE, 0, 0), (M, D, model.SUBTREE, 1, 0),
+                (n_nodes - 1, D, model.SUBTREE, 0, 0)]
+    for j, tpe, flags, _, _ in at_nodes:
+        nodes["type"][j], nodes["flags"][j], nodes["n_content"][j] = tpe, flags, 0
+    nodes["data_start"] = np.cumsum(nodes["n_content"], dtype=np.int64) - nodes["n_content"]
+    has_sub = (nodes["flags"] & model.SUBTREE) != 0
+    nodes["tree_index"] = np.cumsum(has_sub) - has_sub
+    n_data, n_tree = int(nodes["n_content"].sum()), int(has_sub.sum())
+    assert n_nodes > 1024 * 1024 and n_data >= (1 << 21) + 5 and n_data > 2 * 1024 * 1024
+
+    def ids_and_hits(n):
+        i = np.arange(n)
+        ids, hits = np.empty((n, 32), np.uint8), np.ones((n, 2), np.int64)
+        ids[:] = (i % 251 + 1).astype(np.uint8)[:, None]
+        hits[:, 1] = i % 40
+        return ids, hits
+    data_ids, data_hits = ids_and_hits(n_data)
+    tree_ids, tree_hits = ids_and_hits(n_tree)
+    at_ids = (0, 1023, 1024, M - 1, M, M + 1, M + 1024, 2 * M, n_data - 1)
+    for j, i in enumerate(at_ids):  # a null id, a missing id, both at once, in turns
+        if j % 3 != 1:
+            data_ids[i] = 0
+        if j % 3 != 0:
+            data_hits[i] = (0, 0) if j % 2 else (1, model.NO_PACK)
+    for j, _, flags, null, held in at_nodes:
+        if flags & model.SUBTREE:
+            t = int(nodes["tree_index"][j])
+            if null:
+                tree_ids[t] = 0
+            if not held:
+                tree_hits[t] = (0, 0)
+    found, dp, tp = model.level_rule_np(nodes, data_ids, data_hits, tree_ids, tree_hits)
+    want = [tuple(r) for r in found.tolist()]
+    # every chosen place has its findings, and nothing else has one
+    assert sorted({n for n, kind, _ in want if kind in (0, 3, 4, 5)}) == [a[0] for a in at_nodes]
+    assert {kind for _, kind, _ in want} == set(range(6))
+    of_id = lambda i: (int(np.searchsorted(nodes["data_start"], i, "right")) - 1)
+    assert sorted({(n, b) for n, kind, b in want if kind in (1, 2)}) == \
+        sorted((of_id(i), i - int(nodes["data_start"][of_id(i)])) for i in at_ids)
+    assert len(want) == len(at_nodes) + sum((j % 3 != 1) + (j % 3 != 0) for j in range(len(at_ids)))
+    assert len(dp) == 40 and len(tp) == 40
+    _Level.run_arrays(nodes, data_ids, data_hits, tree_ids, tree_hits,
+                      (nodes["type"][has_sub] == D).astype(np.uint8), (want, dp, tp))
 
 
 # ---- check_trees ------------------------------------------------------------------------

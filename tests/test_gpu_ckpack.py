@@ -27,8 +27,10 @@ def _cat(packs):
     return ids, locs, tps, ranges
 
 
-def _run(ids, locs, tps, ranges, hdr=None, cap=None, use_types=True):
-    """The kernel and the model over the same arrays, compared in full."""
+def _run(ids, locs, tps, ranges, hdr=None, cap=None, use_types=True, want_order=True):
+    """The kernel and the model over the same arrays, compared in full.
+    ``want_order`` off: no order array, and the emit pass lists only the packs
+    with findings or a header."""
     from rustic_core_amd.check import CK_FINDING, run_check_packs, sort_max
     d_ids, d_locs = _dev(ids), _dev(locs.view(np.int32))
     d_types = _dev(tps) if use_types else None
@@ -41,7 +43,7 @@ def _run(ids, locs, tps, ranges, hdr=None, cap=None, use_types=True):
                         np.dtype([("type", "<u4"), ("count", "<u4"), ("first", "<u8")]))
         dh = (parsed, recs)
     res = run_check_packs(d_ids, d_locs[:, 1], d_locs[:, 2], d_locs[:, 3], d_types, ranges, hdr=dh,
-                          cap_findings=cap, want_order=True, guard=GUARD)
+                          cap_findings=cap, want_order=want_order, guard=GUARD)
     packs, findings, order = cm.model(ids, locs, tps if use_types else None, ranges, sort_max(), hdr)
     for p, (got, want) in enumerate(zip(res.packs, packs)):
         for k, v in want.items():
@@ -55,6 +57,9 @@ def _run(ids, locs, tps, ranges, hdr=None, cap=None, use_types=True):
     # behind the written records nothing was touched, nor behind any output
     raw_f = res.raw[-1].cpu().numpy()
     assert (raw_f[written * CK_FINDING.itemsize:] == 0xA5).all()
+    if not want_order:
+        assert res.order is None and len(res.raw) == 1
+        return res, packs, findings
     raw_o = res.raw[0].cpu().numpy()
     assert (raw_o[len(ids) * 4:] == 0xA5).all()
     rows = raw_o[:len(ids) * 4].view(np.uint32)
@@ -115,6 +120,12 @@ def test_large_packs_and_the_host_status():
 def _with_headers(rng, counts):
     packs = [cm.random_pack(rng, n, shuffle=bool(i & 1), types=i % 2) for i, n in enumerate(counts)]
     ids, locs, tps, ranges = _cat(packs)
+    return ids, locs, tps, ranges, _headers_of(ids, locs, tps, ranges)
+
+
+def _headers_of(ids, locs, tps, ranges):
+    """The headers of the packs as their packer wrote them: every pack's
+    entries in pack order, under the type of its first entry."""
     h_ids, h_locs, recs = [[], []], [[], []], []
     for (f, c) in ranges:
         t = int(tps[f]) if c else 0
@@ -123,8 +134,7 @@ def _with_headers(rng, counts):
         h_ids[t].append(ids[rows])
         h_locs[t].append(locs[rows])
     cat = lambda parts, w, dt: (np.concatenate(parts) if parts else np.zeros((0, w), dt)).copy()
-    return ids, locs, tps, ranges, ([cat(p, 32, np.uint8) for p in h_ids],
-                                    [cat(p, 4, np.uint32) for p in h_locs], recs)
+    return ([cat(p, 32, np.uint8) for p in h_ids], [cat(p, 4, np.uint32) for p in h_locs], recs)
 
 
 def test_header_compare():
@@ -166,6 +176,79 @@ def test_header_compare():
     assert packs[1]["header_verdict"] == cm.EQUAL
     # without type bytes a pack has its header's type
     _run(ids, locs, None, ranges, hdr, use_types=False)
+
+
+def test_more_packs_than_a_round(gpu_ctx):
+    """4 300 packs of 0 to 6 entries: the sort list and the numbering take
+    more than one round of 1024 packs (``carry``, ``listed``), the sort's grid
+    of 1024 and the emit's of 4096 workgroups walk their lists with a stride.
+    Packs with one wrong type byte and one offset gap stand on both sides of
+    every round's edge, and around a pack that is the host's."""
+    from rustic_core_amd.check import sort_max
+    rng = np.random.default_rng(11)
+    n_packs, host_at = 4300, 3000
+    edges = (0, 1023, 1024, 1025, 2047, 2048, 4095, 4096, n_packs - 1)
+    marked = edges + (host_at - 1, host_at + 1)
+    differ = (4097, 4150, n_packs - 2)
+    assert n_packs > 4 * 1024 + 1 and host_at > 2048 and min(differ) > 4096
+    assert not set(marked) & set(differ)
+    packs = []
+    for pos in range(n_packs):
+        if pos == host_at:
+            packs.append(cm.random_pack(rng, sort_max() + 1, shuffle=True))
+        elif pos in marked:
+            n = int(rng.integers(4, 7))
+            ids, locs, tps = cm.random_pack(rng, n, shuffle=bool(pos & 1), gap=True, types=pos % 2)
+            tps[n - 1] ^= 1  # not the first entry, whose type is the pack's
+            packs.append((ids, locs, tps))
+        elif pos in differ:
+            packs.append(cm.random_pack(rng, 3, shuffle=bool(pos & 1), types=pos % 2))
+        else:
+            n = int(rng.integers(0, 7))
+            packs.append(cm.random_pack(rng, n, shuffle=bool(rng.integers(0, 2)), types=pos % 2))
+    # the packs' entries lie in the arrays in another order than the ranges name them
+    perm = rng.permutation(n_packs)
+    ids, locs, tps, stored = _cat([packs[i] for i in perm])
+    ranges = [None] * n_packs
+    for j, pos in enumerate(perm):
+        ranges[pos] = stored[j]
+    assert [c for _, c in ranges] == [len(p[0]) for p in packs]
+
+    res, model_packs, findings = _run(ids, locs, tps, ranges)
+    shuffled = sum(p["status"] == cm.OK and not p["sorted"] for p in model_packs)
+    assert shuffled > 1024 and res.packs_sorted_on_device == shuffled       # sort list, sort stride
+    assert sum(p["status"] == cm.OK for p in model_packs) > 4096            # emit list, emit stride
+    assert model_packs[host_at]["status"] == cm.HOST and res.packs_host == 1
+    with_findings = [i for i, p in enumerate(model_packs) if p["type_findings"] + p["offset_findings"]]
+    assert with_findings == sorted(marked)
+    for i in marked:  # every entry behind the gap is off its expected offset
+        n = ranges[i][1]
+        assert (model_packs[i]["type_findings"], model_packs[i]["offset_findings"]) == (1, n - n // 2)
+    assert len(findings) == sum(1 + ranges[i][1] - ranges[i][1] // 2 for i in marked)
+    _run(ids, locs, tps, ranges, cap=len(findings) - 1)
+    # without the order and without headers the emit list is the packs with findings alone:
+    # a compaction over five rounds of the numbering
+    assert len({i // 1024 for i in with_findings}) == 5
+    _run(ids, locs, tps, ranges, want_order=False)
+    _run(ids, locs, tps, ranges, want_order=False, cap=len(findings) - 1)
+
+    hdr = _headers_of(ids, locs, tps, ranges)
+    for i in differ:
+        t, c, f = hdr[2][i]
+        hdr[0][t][f + c - 1, 31] ^= 1  # the last byte of the last id
+    res, model_packs, _ = _run(ids, locs, tps, ranges, hdr)
+    for i, p in enumerate(model_packs):
+        if i == host_at:
+            want = (cm.NOT_COMPARED, 0)
+        elif i in differ:
+            want = (cm.DIFFERS, 2)
+        elif i in marked:  # the entry of the wrong type byte is not the header's
+            want = (cm.DIFFERS, p["header_diff"])
+            assert int(tps[cm.pack_order(locs, *ranges[i])[p["header_diff"]]]) != p["type"]
+        else:
+            want = (cm.EQUAL, 0)
+        assert (p["header_verdict"], p["header_diff"]) == want, i
+    _run(ids, locs, tps, ranges, hdr, want_order=False)
 
 
 def test_strided_columns_and_unaligned_ids():

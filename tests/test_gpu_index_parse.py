@@ -110,6 +110,10 @@ def test_tile_edges(gpu_ctx):
     assert one.status == [0] and sum(one.files[0][0]) > 20
     res, m = _check(files, (0, 0), align=tile)
     assert m.status == [0] * (len(files) - 2) + [1, 0]
+    # more tiles and more packs than a round of the two scans of one workgroup: the
+    # counts' (rcdc_ix_count_scan_kernel) and the packs' (rcdc_ix_number_kernel)
+    assert sum((len(f) + tile - 1) // tile for f in files) >= 1220 > 1024
+    assert len(m.packs) > 2 * 1024
     # the same files at offsets that are no multiple of anything
     _check(files[::37] + files[-5:], (7, 9), align=1, shift=11)
 

@@ -159,6 +159,39 @@ def _edge_distances(text, span):
     return blobs, heads
 
 
+def _most_in_a_span(text, span, marker, width):
+    """The most pieces of ``text`` (beginning with ``marker``, ``width`` bytes
+    long at least) that one span of the output touches."""
+    starts, at = [], text.find(marker)
+    while at >= 0:
+        starts.append(at)
+        at = text.find(marker, at + 1)
+    starts = np.array(starts)
+    return max(int(((starts < s + span) & (starts + width > s)).sum()) for s in range(0, len(text), span))
+
+
+def test_more_than_64_pieces_in_a_span(gpu_ctx):
+    """The wave that writes a span takes the span's pack heads and its files
+    64 at a time, one a lane: packs without blobs and empty files, so that a
+    span holds more than 64 of each and both loops take a second pass.  (The
+    loop over blob objects never does: the smallest is 134 bytes long, and a
+    span touches 62 of those at the most, which is asserted here.)"""
+    from rustic_core_amd.index import IndexFile
+    from rustic_core_amd.index_write import write_span
+    span = write_span()
+    blobs = IndexFile(packs=[_pack(900, 300, ints=[(j % 10, 1, 1) for j in range(300)])])
+    assert 60 <= _most_in_a_span(blobs.to_json(), span, b'","type"', 50) <= 64
+    packs = IndexFile(packs=[_pack(1000 + i, 0, i % 2) for i in range(300)])
+    assert _most_in_a_span(packs.to_json(), span, b'{"id":"', 80) > 64
+    for f in (blobs, packs):
+        assert len(f.to_json()) > 2 * span
+        _write([f])
+    empty = [IndexFile(), IndexFile(packs=[_pack(2000, 0)])] * 150
+    assert span // 112 > 64 and all(len(f.to_json()) <= 112 for f in empty)
+    _write(empty)
+    _write([blobs] + empty + [packs])
+
+
 def test_lane_wave_and_span_edges(gpu_ctx):
     from rustic_core_amd.index import IndexFile
     from rustic_core_amd.index_write import write_span
@@ -169,7 +202,9 @@ def test_lane_wave_and_span_edges(gpu_ctx):
     packs = [_pack(100 + i, n, i % 2, T1 if i % 3 == 0 else None) for i, n in enumerate(sizes)]
     _write([IndexFile(packs=packs)] + [IndexFile(packs=[p]) for p in packs])
     # more files than a wave has lanes
-    _write([IndexFile(packs=[_pack(300 + i, i % 4, i % 2)]) for i in range(70)])
+    many = [IndexFile(packs=[_pack(300 + i, i % 4, i % 2)]) for i in range(70)]
+    assert len(many) > 64  # a second round of the wave that places the files, with its carry
+    _write(many)
     # a file of about three spans behind every shift up to the longest object:
     # every byte of a blob object and of a pack head meets a span edge
     body = [_pack(500 + i, 1 + i % 7, i % 2, T1 if i % 2 else None, i * 1001 if i % 3 == 0 else None)

@@ -21,7 +21,6 @@ def _arena(headers, align=1, shift=0):
     """One device arena holding ``headers`` back to back, each at a multiple
     of ``align``, the whole tensor starting ``shift`` bytes past a 16-byte
     boundary; 0xFF wherever no header lies.  Returns (tensor, offs, lens)."""
-    import torch
     offs, o = [], 0
     for h in headers:
         o = (o + align - 1) // align * align
@@ -30,9 +29,16 @@ def _arena(headers, align=1, shift=0):
     host = np.full(o + shift + 1, 0xFF, np.uint8)
     for off, h in zip(offs, headers):
         host[shift + off:shift + off + len(h)] = np.frombuffer(h, np.uint8)
+    return _upload(host, o, shift), offs, [len(h) for h in headers]
+
+
+def _upload(host, o, shift):
+    """``host[shift : shift + o]`` on the device, ``shift`` bytes past a
+    16-byte boundary."""
+    import torch
     t = torch.from_numpy(host).to("cuda:0")
     assert t.data_ptr() % 16 == 0
-    return t[shift:shift + o], offs, [len(h) for h in headers]
+    return t[shift:shift + o]
 
 
 def _check(headers, pack_base=(0, 0), align=1, shift=0, want_ids=(True, True),
@@ -44,28 +50,36 @@ def _check(headers, pack_base=(0, 0), align=1, shift=0, want_ids=(True, True),
     res = parse_headers(d, offs, lens, pack_base, want_ids=want_ids, want_locs=want_locs,
                         guard=GUARD)
     m = model.collect(headers, pack_base)
-    assert res.headers["status"].tolist() == m.status
     names = [n for n in PK_HEADER.names if n != "pad"]
-    got = [model.Record(**{n: int(h[n]) for n in names}) for h in res.headers]
-    assert got == m.records
-    assert res.packs == tuple(m.packs) and res.entries == tuple(len(i) for i in m.ids)
+    assert set(names) == set(model.Record._fields)
+    _compare(res, {n: np.array([getattr(r, n) for r in m.records], np.int64) for n in names}, m.packs,
+             [b"".join(i) for i in m.ids],
+             [np.array(l, np.uint32).reshape(-1, 4) for l in m.locs], want_ids, want_locs)
+    return res, m
+
+
+def _compare(res, records, packs, ids, locs, want_ids=(True, True), want_locs=(True, True)):
+    """Every output of a call against what is expected: ``records`` an array
+    per field of PK_HEADER, ``ids[t]`` the id bytes and ``locs[t]`` (n, 4)
+    uint32 per type; behind what was written the 0xA5 fill and guard."""
+    for n, want in records.items():
+        assert np.array_equal(res.headers[n].astype(np.int64), want), n
+    assert res.packs == tuple(packs) and res.entries == tuple(len(i) // 32 for i in ids)
     raw = iter(res.raw)
     for t in (0, 1):
-        n = len(m.ids[t])
+        n = len(ids[t]) // 32
         if want_ids[t]:
             flat = next(raw).cpu().numpy()
-            assert flat[:n * 32].tobytes() == b"".join(m.ids[t]), t
+            assert flat[:n * 32].tobytes() == ids[t], t
             assert (flat[n * 32:] == 0xA5).all(), t
         else:
             assert res.ids[t] is None
         if want_locs[t]:
             flat = next(raw).cpu().numpy()
-            assert flat[:n * 16].view(np.uint32).reshape(-1, 4).tolist() == \
-                [list(l) for l in m.locs[t]], t
+            assert np.array_equal(flat[:n * 16].view(np.uint32).reshape(-1, 4), locs[t]), t
             assert (flat[n * 16:] == 0xA5).all(), t
         else:
             assert res.locs[t] is None
-    return res, m
 
 
 def _tile():
@@ -178,6 +192,7 @@ def test_one_header_of_65535_entries(gpu_ctx):
     of 64 tiles."""
     h = _long_header(np.random.default_rng(3), 65535, tree=True)
     assert len(h) > 64 * 3 * _tile()
+    assert len(h) // _tile() > 19 * 64  # twenty rounds of the chain's 64 tiles
     res, m = _check([run([0]), h, run([1, 1])], shift=4)
     assert m.status == [OK] * 3 and m.records[1].count == 65535
     assert [r.number for r in m.records] == [0, 0, 1]
@@ -189,6 +204,28 @@ def test_5000_tiny_headers(gpu_ctx):
     hs = [random_header(rng, n_max=4, bad=0.3) for _ in range(5000)]
     _, m = _check(hs, (7, 1 << 20), shift=6)
     assert min(m.packs) > 1024 and m.status.count(OK) < 4900
+
+
+def test_more_headers_than_a_round_of_sums(gpu_ctx):
+    """2^20 + 2100 headers in one call: 1 027 workgroups number them, so the
+    one workgroup over their sums (``block_scan4``) takes a second round with
+    a carry.  Empty headers, one data entry, one tree entry, two compressed
+    entries, and a bad type byte in every 1 000th header (so before and after
+    the 2^20th); every record and both entry arrays are
+    ``pack_header_cases.Pattern``'s arithmetic, which
+    tests/test_pack_header_host.py holds to the model."""
+    from rustic_core_amd.headers import parse_headers
+    from tests.pack_header_cases import PATTERN_EVERY, Pattern
+    n, base = (1 << 20) + 2100, (7, 1 << 20)
+    assert n > 1024 * 1024 and (1 << 20) % PATTERN_EVERY not in (0, PATTERN_EVERY - 1)
+    p = Pattern(n, base)
+    bad = np.nonzero(p.records["status"])[0]
+    assert len(bad) == n // PATTERN_EVERY and bad[-3] < 1 << 20 < bad[-2]
+    o, shift = len(p.arena), 6
+    host = np.full(o + shift + 1, 0xFF, np.uint8)
+    host[shift:shift + o] = p.arena
+    res = parse_headers(_upload(host, o, shift), p.offs, p.lens, base, guard=GUARD)
+    _compare(res, p.records, p.packs, [i.tobytes() for i in p.ids], p.locs)
 
 
 def test_pack_base_and_outputs_off(gpu_ctx):

@@ -9,7 +9,7 @@ import pytest
 from tests import tree_json_model as gt
 from tests import tree_nodes_model as model
 from tests.index_json_cases import hid
-from tests.test_gpu_tree_parse import _arena
+from tests.test_gpu_tree_parse import _arena, _arena_layout, _long_blobs, _many_tile_blobs, _tiles
 from tests.tree_json_cases import (CASES, dir_node, file_node, flipped, other_node, random_text,
                                    random_tree, serialize, tree)
 
@@ -26,24 +26,31 @@ def _check(blobs, align=1, shift=0):
     d, offs, lens = _arena(blobs, align, shift)
     res = parse_tree_nodes(d, offs, lens, guard=GUARD)
     m = model.records(blobs, offs)
-    assert res.blobs["status"].tolist() == m.status
-    got = [tuple(int(b[k]) for k in ("nodes", "data_ids", "tree_ids", "data_start", "tree_start",
-                                     "node_start")) for b in res.blobs]
-    assert got == m.blobs
-    nd, nt, nn = len(m.data_ids), len(m.tree_ids), len(m.nodes)
+    _compare(res, m.status, m.blobs, b"".join(m.data_ids), b"".join(m.tree_ids),
+             np.array(m.is_dir, np.uint8), model.node_array(m.nodes))
+    return res, m, (d, offs, lens)
+
+
+def _compare(res, status, blobs, data_ids, tree_ids, is_dir, want):
+    """Every output of a call against what is expected: the statuses, the six
+    fields per blob (rows of ``blobs``), the id arrays' bytes, ``is_dir`` and
+    the TR_NODE array ``want``; behind them the 0xA5 fill and guard."""
+    assert np.array_equal(res.blobs["status"], np.asarray(status))
+    got = np.stack([res.blobs[k].astype(np.int64) for k in ("nodes", "data_ids", "tree_ids", "data_start",
+                                                            "tree_start", "node_start")], 1)
+    assert np.array_equal(got, np.asarray(blobs, np.int64).reshape(-1, 6))
+    nd, nt, nn = len(data_ids) // 32, len(tree_ids) // 32, len(want)
     assert (res.n_data_ids, res.n_tree_ids, res.nodes) == (nd, nt, nn)
-    assert res.data_ids.cpu().numpy().tobytes() == b"".join(m.data_ids)
-    assert res.tree_ids.cpu().numpy().tobytes() == b"".join(m.tree_ids)
-    assert res.tree_is_dir.cpu().numpy().tolist() == m.is_dir
+    assert res.data_ids.cpu().numpy().tobytes() == bytes(data_ids)
+    assert res.tree_ids.cpu().numpy().tobytes() == bytes(tree_ids)
+    assert np.array_equal(res.tree_is_dir.cpu().numpy(), is_dir)
     assert tuple(res.node_records.shape) == (nn, 32)
-    want = model.node_array(m.nodes)
     have = res.nodes_host()
     for k in want.dtype.names:
-        assert have[k].tolist() == want[k].tolist(), k
+        assert np.array_equal(have[k], want[k]), k
     for flat, used in zip(res.raw, (nd * 32, nt * 32, nt, nn * 32)):
         assert (flat[used:].cpu().numpy() == 0xA5).all()
         assert int(flat.numel()) >= used + GUARD
-    return res, m, (d, offs, lens)
 
 
 def test_case_table(gpu_ctx):
@@ -112,12 +119,15 @@ def _node(i, n_ids=None):
 
 def test_counts_around_a_wave_and_a_workgroup(gpu_ctx):
     """63, 64, 65 and 257 nodes in a blob, a file of 4097 ids, 1 and 257
-    blobs: across the 1024-record blocks of the numbering's scan."""
+    blobs: across the waves of the numbering's scan.  Every call here holds
+    fewer than 1024 nodes, one workgroup of the numbering; more than one is
+    ``test_numbering_over_workgroups``, more than one round of their sums
+    ``test_numbering_past_a_round_of_sums``."""
     blobs = [serialize(tree(*[_node(i) for i in range(n)])) for n in (63, 64, 65, 257, 0)]
     blobs.append(serialize(tree(file_node("before", [1]), file_node("big", [j % 256 for j in range(4097)]),
                                 {"name": "after", "type": "dir"})))
     res, m, _ = _check(blobs, align=1, shift=3)
-    assert m.status == [0] * len(blobs)
+    assert m.status == [0] * len(blobs) and 64 * 4 < len(m.nodes) < 1024
     assert [b[0] for b in m.blobs] == [63, 64, 65, 257, 0, 3]
     assert m.nodes[-1][3] == len(m.data_ids) and m.nodes[-2][4] == 4097
     _check(blobs[3:4])
@@ -126,6 +136,95 @@ def test_counts_around_a_wave_and_a_workgroup(gpu_ctx):
             for i in range(257)]
     res, m, _ = _check(many, align=1, shift=9)
     assert sum(m.status) == 51 and len(m.nodes) > 700
+
+
+@pytest.mark.parametrize("n", (1025, 2049))
+def test_numbering_over_workgroups(gpu_ctx, n):
+    """``n`` node records from one call: the numbering runs in two and in
+    three workgroups of 1024 nodes, and their sums are added back.  Blobs
+    outside G_N, whose nodes are counted by no record, stand before and after
+    the 1024th node of every workgroup's edge."""
+    by_name = {c[0]: c[1] for c in model.TABLE}
+    bad = [by_name["unknown_key"],
+           serialize(tree(_node(1), _node(5), {"name": "z", "type": "file", "bogus": 1}, _node(6)))]
+    assert not any(model.in_gn(b) for b in bad)
+    blob = lambda first, count: serialize(tree(*[_node(first + i) for i in range(count)]))
+    blobs = [blob(0, 700), bad[0], blob(700, 300), bad[1], blob(1000, 24), bad[0], blob(1024, 1)]
+    if n == 2049:
+        blobs += [bad[1], blob(1025, 1000), bad[0], blob(2025, 23), bad[1], blob(2048, 1)]
+    res, m, _ = _check(blobs, align=1, shift=7)
+    assert len(m.nodes) == n and (n - 1) // 1024 == (1 if n == 1025 else 2)
+    assert sum(m.status) == (3 if n == 1025 else 6)
+    # the parser numbers every node of the text, the rejected blobs' too: they shift
+    # a node's place in its workgroup, not its record
+    assert res.nodes == n and [b[5] for b in m.blobs][-1] == n - 1
+
+
+def test_more_tiles_than_a_scan_round(gpu_ctx):
+    """tests/test_gpu_tree_parse.py's test of this name through
+    rcdc_tree_nodes: 2 100 blobs, more than 2 048 tiles, three rounds of the
+    scan over the tiles' counts."""
+    from rustic_core_amd.tree import parse_tile
+    tile = parse_tile()
+    at = _ITEMS["escaped_quote"]
+    assert _EDGE[at - 1:at + 1] == b'\\"'
+    blobs = _many_tile_blobs(_node, _EDGE, at, [c[1] for c in model.TABLE if not c[3]], tile)
+    offs, lens, _ = _arena_layout(blobs, tile)
+    assert len(blobs) >= 2100 and _tiles(offs, lens, tile) > 2 * 1024
+    res, m, _ = _check(blobs, align=tile)
+    assert 20 <= sum(m.status) < 40 and len(m.nodes) > 4000
+    assert sum(bool(nd[7] & model.NAME_ESC) for nd in m.nodes) >= 40
+
+
+def test_a_blob_of_three_state_rounds(gpu_ctx):
+    """tests/test_gpu_tree_parse.py's blobs of more than 128 tiles through
+    rcdc_tree_nodes: the names behind the long file and behind the string
+    that crosses the second round's edge are where the model finds them."""
+    from rustic_core_amd.tree import parse_tile
+    tile = parse_tile()
+    blobs = _long_blobs(tile)
+    res, m, _ = _check(blobs, align=tile)
+    assert m.status == [0, 0] and [b[0] for b in m.blobs] == [5, 4]
+    m_offs, _, _ = _arena_layout(blobs, tile)
+    raw = lambda b, nd: blobs[b][nd[0] - m_offs[b]:nd[0] - m_offs[b] + nd[1]]
+    assert [raw(0, nd) for nd in m.nodes[:5]] == [b"big", b'q\\"uote', b"]}[{", b"back\\\\slash", b"last"]
+    assert [raw(1, nd) for nd in m.nodes[5:]] == [b"big", b"f", b"d", b"g"]
+
+
+def test_numbering_past_a_round_of_sums(gpu_ctx):
+    """2^20 + 2100 node records in one call, and the nodes of two rejected
+    blobs besides: 1 029 workgroups number them, so the one workgroup over
+    their sums (``block_scan4``) takes a second round with a carry.  The
+    blobs and every expected output are tests/tree_numbering_cases.py's
+    arithmetic, held to the models by tests/test_tree_numbering_host.py.  A
+    rejected blob stands before the 2^20th node and one behind it; the same
+    arena through rcdc_tree_parse gives the same but for the records."""
+    from rustic_core_amd.tree import parse_tree_nodes, parse_trees
+    from tests import tree_numbering_cases as cases
+    counts = [32001 + 37 * i for i in range(31)]
+    counts = counts[:5] + [1001] + counts[5:] + [40000, 999, 1440]
+    bad = [0] * len(counts)
+    bad[5], bad[-2] = cases.BAD_KEY, cases.BAD_END
+    before = np.cumsum(counts) - counts
+    assert before[5] + counts[5] < 1 << 20 < before[-2] and before[-3] < 1 << 20
+    e = cases.Expected(counts, bad, align=16)
+    assert len(e.nodes) == (1 << 20) + 2100 and len(e.nodes) > 1024 * 1024
+    assert sum(len(t) for t in e.texts) < 64 << 20
+    d, offs, lens = _arena(e.texts, align=16)
+    assert offs == e.offs
+    res = parse_tree_nodes(d, offs, lens, guard=GUARD)
+    _compare(res, e.status, e.blobs, e.data_ids, e.tree_ids, e.is_dir, e.nodes)
+    old = parse_trees(d, offs, lens, guard=GUARD)
+    assert np.array_equal(old.blobs["status"], e.status)
+    for k, col in zip(("nodes", "data_ids", "tree_ids", "data_start", "tree_start"), e.blobs.T):
+        assert np.array_equal(old.blobs[k].astype(np.int64), col), k
+    assert (old.n_data_ids, old.n_tree_ids, old.nodes) == (len(e.data_ids) // 32, len(e.tree_ids) // 32,
+                                                           len(e.nodes))
+    assert old.data_ids.cpu().numpy().tobytes() == e.data_ids
+    assert old.tree_ids.cpu().numpy().tobytes() == e.tree_ids
+    assert np.array_equal(old.tree_is_dir.cpu().numpy(), e.is_dir)
+    for flat, used in zip(old.raw, (len(e.data_ids), len(e.tree_ids), len(e.is_dir))):
+        assert (flat[used:].cpu().numpy() == 0xA5).all() and int(flat.numel()) >= used + GUARD
 
 
 def test_random_trees(gpu_ctx):

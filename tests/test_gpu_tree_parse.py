@@ -15,17 +15,23 @@ pytestmark = pytest.mark.gpu
 GUARD = 256
 
 
+def _arena_layout(blobs, align=1):
+    """(offs, lens, the arena's length) of ``_arena``."""
+    offs, o = [], 0
+    for f in blobs:
+        o = (o + align - 1) // align * align
+        offs.append(o)
+        o += len(f) + (1 if align == 1 else 0)
+    return offs, [len(f) for f in blobs], o
+
+
 def _arena(blobs, align=1, shift=0):
     """One device arena holding ``blobs``: each at a multiple of ``align``,
     the whole tensor starting ``shift`` bytes past a 16-byte boundary (0xFF
     between the blobs, so a read past a blob's end does not look like
     whitespace).  Returns (tensor, offs, lens)."""
     import torch
-    offs, o = [], 0
-    for f in blobs:
-        o = (o + align - 1) // align * align
-        offs.append(o)
-        o += len(f) + (1 if align == 1 else 0)
+    offs, _, o = _arena_layout(blobs, align)
     host = np.full(o + shift + 1, 0xFF, np.uint8)
     for off, f in zip(offs, blobs):
         host[shift + off:shift + off + len(f)] = np.frombuffer(f, np.uint8)
@@ -178,6 +184,91 @@ def test_counts_around_a_wave_and_a_workgroup(gpu_ctx):
             for i in range(257)]
     res, m = _check(many, align=1, shift=9)
     assert sum(m.status) == 51 and m.nodes > 500
+
+
+def _tiles(offs, lens, tile, shift=0):
+    """The tiles of a call as the parser counts them: a blob's first tile
+    starts at the 16-byte boundary at or before its first byte."""
+    return sum(((o + shift) % 16 + n + tile - 1) // tile for o, n in zip(offs, lens) if n)
+
+
+def _many_tile_blobs(node, edge, quote_at, rejected, tile, n=2100):
+    """``n`` blobs of a few spaces and a tree of 1 to 3 ``node``s each; every
+    50th is ``edge`` moved so that the escaped quote of its name (at
+    ``quote_at``) is the first byte of the blob's second tile and its
+    backslash the last of the first; every 97th is one of ``rejected``."""
+    blobs = []
+    for i in range(n):
+        if i % 97 == 96:
+            blobs.append(rejected[(i // 97) % len(rejected)])
+        elif i % 50 == 49:
+            blobs.append(b" " * (tile - quote_at) + edge)
+        else:
+            blobs.append(b" " * (i % 5) + serialize(tree(*[node(i + k) for k in range(1 + i % 3)])))
+    return blobs
+
+
+def test_more_tiles_than_a_scan_round(gpu_ctx):
+    """2 100 blobs at multiples of the tile, more than 2 048 tiles: the one
+    workgroup that scans the tiles' counts (``block_scan4``) takes three
+    rounds of 1024 and carries the totals from round to round.  Blobs of two
+    tiles and rejected blobs stand among them, so a tile's rank is not its
+    blob's number."""
+    from rustic_core_amd.tree import parse_tile
+    tile = parse_tile()
+    at = _ITEMS["escaped_quote"]
+    assert _EDGE[at - 1:at + 1] == b'\\"'
+    blobs = _many_tile_blobs(_node, _EDGE, at, [c[1] for c in CASES if not c[2]], tile)
+    offs, lens, _ = _arena_layout(blobs, tile)
+    assert len(blobs) >= 2100 and _tiles(offs, lens, tile) > 2 * 1024
+    assert all(lens[i] > tile for i in range(49, len(blobs), 50) if i % 97 != 96)
+    res, m = _check(blobs, align=tile)
+    assert 20 <= sum(m.status) < 40 and m.nodes > 4000
+    # a rejected blob and a blob of two tiles on either side of both round edges
+    first = np.cumsum([0] + [(n + tile - 1) // tile for n in lens])
+    for edge in (1024, 2048):
+        b = int(np.searchsorted(first, edge, "right")) - 1
+        near = range(b - 100, b + 100)
+        assert any(m.status[i] for i in near if i < b) and any(m.status[i] for i in near if i > b)
+        assert any(lens[i] > tile for i in near if i < b) and any(lens[i] > tile for i in near if i > b)
+
+
+def _long_blobs(tile):
+    """Two blobs of 130 to 140 tiles: a file of 8 400 ids and behind it nodes
+    whose names hold an escaped quote, brackets and a backslash; and one in
+    which a string (a ``user`` of brackets and escaped quotes) begins in tile
+    127 and ends in tile 129, so the state carried into the third round of 64
+    tiles is inside a string."""
+    ids = [j % 256 for j in range(8400)]
+    one = serialize(tree(file_node("big", ids), dict(file_node("NAME1", [1, 2]), user="u"),
+                         dir_node("NAME2", 7), dict(file_node("NAME3", [3]), group="g"),
+                         other_node("last", "fifo"))) \
+        .replace(b"NAME1", b'q\\"uote').replace(b"NAME2", b"]}[{").replace(b"NAME3", b"back\\\\slash")
+    head = serialize(tree(file_node("big", ids[:7800]), dict(file_node("f", [5]), user="USER"),
+                          dir_node("d", 9), file_node("g", [6, 7])))
+    start = head.index(b"USER")
+    fill = b'x]}[{\\"y[{' * (2 * tile // 10)
+    value = fill[:(129 * tile + 100) - start]
+    assert value[-2:-1] != b"\\"  # the value does not end inside an escape
+    two = head.replace(b"USER", value)
+    assert start // tile == 127 and (start + len(value)) // tile == 129
+    return [one, two]
+
+
+def test_a_blob_of_three_state_rounds(gpu_ctx):
+    """``tile_state`` walks a blob's tiles 64 at a time with one wave; these
+    blobs have more than 128 tiles, so the state is carried over two round
+    edges, the second time out of a carried state."""
+    from rustic_core_amd.tree import parse_tile
+    tile = parse_tile()
+    blobs = _long_blobs(tile)
+    for b in blobs:
+        assert 130 <= (len(b) + tile - 1) // tile <= 140 and model.in_gt(b)
+    res, m = _check(blobs, align=tile)
+    assert m.status == [0, 0] and [b[0] for b in m.blobs] == [5, 4]
+    assert m.blobs[0][1] == 8400 + 3 and m.blobs[1][1] == 7800 + 3
+    # and behind a short blob, off the tile's grid
+    _check([blobs[1][-300:], blobs[1], blobs[0]], align=16)
 
 
 def test_random_trees(gpu_ctx):

@@ -75,6 +75,25 @@ def test_collect():
             assert r.pack_size == p.pack_size() and r.size == 32 + len(h)
 
 
+def test_pattern_against_the_model():
+    """The arithmetic of ``pack_header_cases.Pattern`` (what the device test
+    of more than 2^20 headers expects) against ``collect`` at 3 000 headers:
+    every field of every record and both entry arrays in full."""
+    from tests.pack_header_cases import Pattern
+    p = Pattern(3000, (7, 1 << 20))
+    hs = p.headers()
+    assert len(hs) == 3000 and hs[:4] == [b"", hs[1], hs[2], hs[3]] and hs[999][0] == 4
+    assert [len(h) for h in hs[:4]] == [0, 37, 37, 82] and len({h[5:9] for h in hs[1::4]}) == 750
+    c = model.collect(hs, (7, 1 << 20))
+    assert c.status.count(BAD_TYPE) == 3 and c.status.count(OK) == 2997
+    for k in model.Record._fields:
+        assert [getattr(r, k) for r in c.records] == p.records[k].tolist(), k
+    assert c.packs == p.packs
+    for t in (0, 1):
+        assert b"".join(c.ids[t]) == p.ids[t].tobytes(), t
+        assert [list(l) for l in c.locs[t]] == p.locs[t].tolist(), t
+
+
 def test_bound_and_tile():
     from rustic_core_amd import _lib, headers
     L = _lib.lib()

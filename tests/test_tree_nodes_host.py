@@ -152,6 +152,44 @@ def test_level_rule_of_the_model_agrees():
     assert (dp, tp, packs) == ({7}, {9}, {"P7", "P9"})
 
 
+@pytest.mark.parametrize("seed", range(6))
+def test_level_rule_in_numpy_agrees(seed):
+    """``level_rule_np`` (the reference of the level of 2^20 nodes in
+    tests/test_gpu_check_trees.py) against ``level_rule`` on random levels:
+    every type, nodes with and without content and subtree, null ids, ids the
+    index lacks, both, and hits whose pack is NO_PACK."""
+    rng = np.random.default_rng(seed)
+    null = bytes(32)
+    nodes, data_ids, data_hits, tree_ids, tree_hits = [], [], [], [], []
+
+    def an_id():
+        return null if rng.random() < 0.2 else bytes(rng.integers(1, 256, 32, dtype=np.uint8))
+
+    def a_hit():
+        r = rng.random()
+        return (0, 0) if r < 0.2 else (1, model.NO_PACK) if r < 0.3 else (1, int(rng.integers(0, 30)))
+    for _ in range(int(rng.integers(1, 120))):
+        tpe = int(rng.choice([0, 0, 0, 1, 1, 2, 5]))
+        content = rng.random() < 0.8
+        nc = int(rng.integers(0, 6)) if content else 0
+        sub = rng.random() < (0.8 if tpe == 1 else 0.2)
+        nodes.append((0, 0, 0, len(data_ids), nc, len(tree_ids), tpe,
+                      (model.CONTENT if content else 0) | (model.SUBTREE if sub else 0), 0))
+        if tpe == 0:
+            for _ in range(nc):
+                data_ids.append(an_id())
+                data_hits.append(a_hit())
+        if sub:
+            tree_ids.append(an_id())
+            tree_hits.append(a_hit())
+    want = model.level_rule(nodes, data_ids, data_hits, tree_ids, tree_hits)
+    arr = lambda ids: np.frombuffer(b"".join(ids), np.uint8).reshape(-1, 32)
+    found, dp, tp = model.level_rule_np(model.node_array(nodes), arr(data_ids), data_hits,
+                                        arr(tree_ids), tree_hits)
+    assert [tuple(r) for r in found.tolist()] == want[0] and (dp, tp) == want[1:]
+    assert seed or len({k for _, k, _ in want[0]}) == 6  # every kind
+
+
 # ---- the recorded repositories ----------------------------------------------------------
 
 def test_tree_blobs_of_the_recorded_repositories_outside_gn(oracle_mod, monkeypatch, capsys):

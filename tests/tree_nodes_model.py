@@ -220,6 +220,52 @@ def level_rule(nodes, data_ids, data_hits, tree_ids, tree_hits):
     return found, dp, tp
 
 
+def level_rule_np(nodes, data_ids, data_hits, tree_ids, tree_hits):
+    """``level_rule`` in numpy, for levels too large for it (held to it by
+    tests/test_tree_nodes_host.py): ``nodes`` a TR_NODE array, the ids (n, 32)
+    uint8, the hits (n, 2) arrays of (count, pack).  Returns the findings as an
+    (n, 3) int64 array of (node, kind, blob_num) in the rule's order, and the
+    two sets of marked packs."""
+    tpe, flags = nodes["type"], nodes["flags"]
+    d0, nc = nodes["data_start"].astype(np.int64), nodes["n_content"].astype(np.int64)
+    data_hits = np.asarray(data_hits, np.int64).reshape(-1, 2)
+    tree_hits = np.asarray(tree_hits, np.int64).reshape(-1, 2)
+    miss = lambda h: (h[:, 0] == 0) | (h[:, 1] == NO_PACK)
+    # per id of the arrays once, then picked per judged id: no row is copied
+    is_null = lambda ids: ~np.ascontiguousarray(ids).view(np.uint64).reshape(-1, 4).any(1) \
+        if len(ids) else np.zeros(0, bool)
+    k_all = np.arange(len(nodes), dtype=np.int64)
+    rows = []  # (node, blob_num, kind): the rule's order is this tuple's
+
+    def add(k, num, kind):
+        rows.append(np.stack([k, num, np.full(len(k), kind, np.int64)], 1))
+    files = tpe == 0
+    with_content = files & ((flags & CONTENT) != 0)
+    k = k_all[files & ~with_content]
+    add(k, np.zeros(len(k), np.int64), 0)
+    k, n = k_all[with_content], nc[with_content]
+    of_id = np.repeat(k, n)                                    # the node of every judged id
+    num = np.arange(len(of_id), dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+    at = np.repeat(d0[with_content], n) + num
+    null, lacks = is_null(data_ids)[at], miss(data_hits)[at]
+    add(of_id[null], num[null], 1)
+    add(of_id[lacks], num[lacks], 2)
+    dp = set(np.unique(data_hits[:, 1][at[~lacks]]).tolist())
+    dirs = tpe == 1
+    with_sub = dirs & ((flags & SUBTREE) != 0)
+    k = k_all[dirs & ~with_sub]
+    add(k, np.zeros(len(k), np.int64), 3)
+    k, t = k_all[with_sub], nodes["tree_index"][with_sub].astype(np.int64)
+    null = is_null(tree_ids)[t]
+    lacks = ~null & miss(tree_hits)[t]
+    add(k[null], np.zeros(int(null.sum()), np.int64), 4)
+    add(k[lacks], np.zeros(int(lacks.sum()), np.int64), 5)
+    tp = set(np.unique(tree_hits[:, 1][t[~null & ~lacks]]).tolist())
+    found = np.concatenate(rows)
+    found = found[np.lexsort((found[:, 2], found[:, 1], found[:, 0]))]
+    return found[:, [0, 2, 1]], dp, tp
+
+
 # Tree blobs of the reference's recorded check repositories (tests/check_cases.py) that
 # lie outside G_N, counted by tests/test_tree_nodes_host.py: what the device route of
 # check_trees leaves to the host there.
