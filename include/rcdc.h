@@ -1394,6 +1394,71 @@ rcdc_status rcdc_check_trees_level(rcdc_ctx *ctx, const rcdc_trnode *d_nodes, ui
                                    rcdc_cktree_finding *d_findings, uint64_t cap_findings,
                                    uint64_t *n_findings, void *hip_stream);
 
+/* ---- the verdict of `repair snapshots` (commands/repair/snapshots.rs,
+ * blob/tree/modify.rs) ---------------------------------------------------------
+ * Every distinct tree id of the walk has a slot: its entry number in an
+ * id-only rcdc_dindex, which rcdc_dindex_lookup returns as hit.entry.  A tree
+ * is damaged where the repair rule rewrites it for a reason of its own: a
+ * "file" node with a content id the data index lacks (hit.count == 0 or
+ * hit.loc.pack == RCDC_DINDEX_NO_PACK; an all-zero id is looked up like any
+ * other), or a "dir" node without a subtree.  It is changed where it is
+ * damaged or a tree under one of its "dir" nodes is changed.
+ *
+ * rcdc_repair_trees_level, one call per batch of rcdc_tree_nodes.  In HBM:
+ * the node records; the hit records of d_data_ids in the data index; the hit
+ * records of d_tree_ids in the id-only set of the walk, looked up after the
+ * subtrees of this batch's "dir" nodes are in it; d_tree_is_dir; d_blob_slot,
+ * the slot of each blob of the batch.  It writes d_damaged[slot] = 1 (plain
+ * byte stores; nothing else of d_damaged is touched) for the blob of every
+ * damaged node, and one edge per entry of d_tree_ids at the entry's place:
+ * (slot of the node's blob, hit.entry of the subtree) for the subtree of a
+ * "dir" node, (RCDC_REPAIR_NO_EDGE, RCDC_REPAIR_NO_EDGE) for that of any other
+ * type, for a subtree the set lacks and for a blob or subtree slot not below
+ * n_slots.  *result (host): the content ids of "file" nodes that the index
+ * lacks, the damaged nodes, the "file" nodes whose content is absent or null
+ * and the lowest index of such a node (RCDC_REPAIR_NO_NODE where there is
+ * none); the reference panics on such a node, so the caller refuses the run.
+ * A lane per id finds its node by a search over data_start, a lane per node
+ * does the rest; no lane loops over a node's ids.
+ *
+ * rcdc_repair_spread.  d_changed becomes the least fixed point of
+ * changed[p] |= changed[c] over the n_edges edges (p, c), starting from
+ * d_damaged (the two may be the same array): rounds of one kernel, a lane per
+ * edge, until a round sets nothing.  Edges with an end not below n_slots (so
+ * RCDC_REPAIR_NO_EDGE) are skipped.  It ends on any edge list, cycles
+ * included, after at most n_slots + 1 rounds.  *rounds (host): the rounds up
+ * to and including the first that set nothing (0 without edges or slots);
+ * RCDC_REPAIR_SPREAD_ROUNDS rounds are launched between two reads of their
+ * "set something" words.
+ *
+ * Refused before anything is launched: a null context, result or rounds, a
+ * null array whose count is not 0, arrays not aligned (16 bytes for records, 8
+ * for edges, 4 for hits and slots), 2^32 - 1 or more of anything counted.     */
+#define RCDC_REPAIR_NO_EDGE 0xFFFFFFFFu
+#define RCDC_REPAIR_NO_NODE 0xFFFFFFFFFFFFFFFFull
+#define RCDC_REPAIR_SPREAD_ROUNDS 8u
+typedef struct {
+    uint32_t parent, child; /* slots */
+} rcdc_repair_edge; /* 8 B */
+typedef struct {
+    uint64_t missing_ids;
+    uint64_t damaged_nodes;
+    uint64_t files_without_content;
+    uint64_t first_without_content; /* a node index, or RCDC_REPAIR_NO_NODE */
+} rcdc_repair_level_result; /* 32 B */
+rcdc_status rcdc_repair_trees_level(rcdc_ctx *ctx, const rcdc_trnode *d_nodes, uint64_t n_nodes,
+                                    const rcdc_dindex_hit *d_data_hits, uint64_t n_data_ids,
+                                    const uint8_t *d_tree_is_dir,
+                                    const rcdc_dindex_hit *d_tree_hits, uint64_t n_tree_ids,
+                                    const uint32_t *d_blob_slot, uint64_t n_blobs,
+                                    uint8_t *d_damaged, uint64_t n_slots,
+                                    rcdc_repair_edge *d_edges, rcdc_repair_level_result *result,
+                                    void *hip_stream);
+rcdc_status rcdc_repair_spread(rcdc_ctx *ctx, const rcdc_repair_edge *d_edges, uint64_t n_edges,
+                               const uint8_t *d_damaged, uint8_t *d_changed, uint64_t n_slots,
+                               uint64_t *rounds, void *hip_stream);
+uint32_t rcdc_repair_spread_rounds_per_launch(void); /* RCDC_REPAIR_SPREAD_ROUNDS */
+
 /* ---- pack headers parsed on the device (repofile/packfile.rs) --------------
  * What PackHeader::from_binary (packfile.rs:88-242) reads out of the table at
  * the end of a pack, for a batch of opened (plaintext) headers in HBM:

@@ -30,6 +30,9 @@ from .headers import (  # noqa: F401
     HeaderResult, PackChecker, ParsedHeaders, RepairReport, index_checked, parse_headers,
     read_headers, repair_index,
 )
+from .repair import (  # noqa: F401
+    RepairPlan, RepairResult, RepairSnapshotsOptions, apply_repair, plan_repair, repair_snapshots,
+)
 
 __all__ = [
     "ErrorKind", "RusticError", "Chunker", "ChunkIter", "ConfigFile", "Context",
@@ -41,4 +44,6 @@ __all__ = [
     "ParsedTrees", "find_used_blobs", "parse_tree_host", "parse_trees", "snapshot_trees",
     "HeaderResult", "PackChecker", "ParsedHeaders", "RepairReport", "index_checked",
     "parse_headers", "read_headers", "repair_index",
+    "RepairPlan", "RepairResult", "RepairSnapshotsOptions", "apply_repair", "plan_repair",
+    "repair_snapshots",
 ]

@@ -51,6 +51,7 @@ EXPORTS = (
     "rcdc_tree_nodes", "rcdc_tree_nodes_bound", "rcdc_tree_names", "rcdc_check_trees_level",
     "rcdc_pack_header_parse", "rcdc_pack_header_parse_bound", "rcdc_pack_header_parse_tile",
     "rcdc_check_packs", "rcdc_check_packs_sort_max",
+    "rcdc_repair_trees_level", "rcdc_repair_spread", "rcdc_repair_spread_rounds_per_launch",
 )
 ABI_VERSION = 5
 
@@ -146,6 +147,13 @@ class CkpackResult(ctypes.Structure):
     """rcdc_ckpack_result."""
     _fields_ = [("findings", ctypes.c_uint64), ("packs_host", ctypes.c_uint64),
                 ("packs_sorted_on_device", ctypes.c_uint64)]
+
+
+class RepairLevelResult(ctypes.Structure):
+    """rcdc_repair_level_result."""
+    _fields_ = [("missing_ids", ctypes.c_uint64), ("damaged_nodes", ctypes.c_uint64),
+                ("files_without_content", ctypes.c_uint64),
+                ("first_without_content", ctypes.c_uint64)]
 
 
 class PruneResult(ctypes.Structure):
@@ -402,6 +410,13 @@ def lib() -> ctypes.CDLL:
     L.rcdc_check_packs.restype = st
     L.rcdc_check_packs.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64,
                                    vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
+    L.rcdc_repair_trees_level.restype = st
+    L.rcdc_repair_trees_level.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp,
+                                          P(RepairLevelResult), vp]
+    L.rcdc_repair_spread.restype = st
+    L.rcdc_repair_spread.argtypes = [vp, vp, u64, vp, vp, u64, P(u64), vp]
+    L.rcdc_repair_spread_rounds_per_launch.restype = u32
+    L.rcdc_repair_spread_rounds_per_launch.argtypes = []
     _lib = L
     return L
 

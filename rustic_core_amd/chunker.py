@@ -68,6 +68,8 @@ class ConfigFile:
     # blob processing (configfile.rs:43-50)
     compression: Optional[int] = None
     extra_verify: Optional[bool] = None
+    # configfile.rs: snapshots may not be removed (repair.py refuses to)
+    append_only: Optional[bool] = None
 
     @classmethod
     def new(cls, version: int, poly: int) -> "ConfigFile":

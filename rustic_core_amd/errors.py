@@ -17,6 +17,7 @@ class ErrorKind(enum.Enum):
     Cryptography = "Cryptography"    # crypto/aespoly1305.rs:89-108 (MAC check)
     Verification = "Verification"    # backend/decrypt.rs:516-526 (extra_verify)
     Repository = "Repository"        # commands/check.rs:962-974 (check found errors)
+    AppendOnly = "AppendOnly"        # commands/repair/snapshots.rs:169-174 (delete, append-only)
 
 
 class RusticError(Exception):
